@@ -14,6 +14,13 @@ DarkRoom 10x10, H=100, Heps=40, 4096 tasks/GPU).
 
 Prints ONE JSON line on rank 0.  Launch: python bench.py [--gpus N --steps K --warmup W]
 (multi-GPU: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...).
+
+A plain run sets up, warms up, times the K steps and prints the line (for the bandit workloads
+with the roofline of the timed launches, which costs no run of its own).  --dump-outputs DIR
+also writes what the last timed step returned as DIR/<name>.npy.  --full adds everything that
+takes runs of its own: the CPU baselines, the stream-ceiling probe, the DarkRoom roofline (a
+replayed step that counts the window forwards) and the darkroom_c3 / darkroom_c5_shard /
+linear_c4_shard sub-objects (--no-cpu-baseline, --no-darkroom, --no-linear drop parts of it).
 """
 import argparse
 import json
@@ -215,6 +222,23 @@ def stream_ceiling(N, H, n_layer, pin_positions, kernel_ms):
                     "frac = floor / rollout kernel_ms (1.0 = the launch reads at its layout's measured ceiling)"}
 
 
+DUMP_ARRAY_BYTES = 16 << 20  # per array; a step returns at most three large arrays (< 64 MB in all)
+
+
+def dump_outputs(path, arrays):
+    """Write what the last timed step returned as path/<name>.npy: float64 stays float64, every
+    other dtype (float32, the int32 actions: exact) becomes float32.  An array above
+    DUMP_ARRAY_BYTES is cut to a fixed, seeded sample of its rows (the same rows every run)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > DUMP_ARRAY_BYTES and a.ndim >= 1:
+            keep = max(1, DUMP_ARRAY_BYTES // max(1, a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def run_timed(one, steps, warmup, dist, backend, kernel_only):
     """W untimed warmup steps, then K steps bracketed by a barrier + synchronize on both sides;
     returns (elapsed s max over ranks, kernel ms: the rollout launch alone when kernel_only else
@@ -245,9 +269,10 @@ def run_timed(one, steps, warmup, dist, backend, kernel_only):
     return elapsed, kern_ms
 
 
-def darkroom_workload(L, H, Heps, N, first, count, n_total, dist, memo):
+def darkroom_workload(L, H, Heps, N, first, count, n_total, dist, memo, keep_last=False):
     """BASELINE config 3 (config 5's per-GPU shard for --tasks 8192): the DarkRoom online eval
-    (evals/eval_darkroom.py:20-84, DPT sampling controller) over this rank's task block."""
+    (evals/eval_darkroom.py:20-84, DPT sampling controller) over this rank's task block.
+    keep_last: the dict's "last" holds what the latest step returned (for --dump-outputs)."""
     import dpt_hip
     from ctrls.ctrl_darkroom import DarkroomTransformerController
     from dpt_hip.distributed import gather_rows
@@ -262,6 +287,7 @@ def darkroom_workload(L, H, Heps, N, first, count, n_total, dist, memo):
     goals_all = goals[np.arange(n_total) % 100]
     envs = [DarkroomEnv(10, g, H) for g in goals_all[first:first + count]]
     vec = DarkroomEnvVec(envs, first_task=first)
+    last = {}
 
     def one(step_idx, ev=None):
         np.random.seed(step_idx)
@@ -269,6 +295,8 @@ def darkroom_workload(L, H, Heps, N, first, count, n_total, dist, memo):
         ret = eval_darkroom.deploy_online_vec(vec, ctrl, Heps, H, H)
         if dist is not None:  # the per-task returns of every rank (online regret all-gather)
             gather_rows(torch.from_numpy(ret).cuda(), n_total)
+        if keep_last:
+            last["returns"] = ret
         return ret
 
     def roofline(kern_ms):
@@ -326,14 +354,16 @@ def darkroom_workload(L, H, Heps, N, first, count, n_total, dist, memo):
     dtype = ("f16x2-split MFMA products (fp32 accumulate, ~2^-21/product) + f32 VALU / "
              "f32 selection cdf (f64 within 2^-15 of an edge); int32 grid")
     return dict(one=one, roofline=roofline, env_steps=n_total * Heps * H, workload=workload, dtype=dtype,
-                cfg={"tasks_per_gpu": N, "horizon": H, "episodes": Heps}, sd=sd, goals=goals_all)
+                cfg={"tasks_per_gpu": N, "horizon": H, "episodes": Heps}, sd=sd, goals=goals_all, last=last)
 
 
-def bandit_workload(wl, L, H, var, first, count, n_total, rank):
+def bandit_workload(wl, L, H, var, first, count, n_total, rank, keep_last=False):
     """BASELINE config 2 (wl "bandit": 5 arms, H=500, means ~ U(0,1)) or config 4's per-GPU shard
     (wl "linear": 20 arms, H=1000, collect_data.py:230-231 arms, theta ~ N(0,1)/sqrt(2)): the
     online eval (evals/eval_bandit.py:56-103 / eval_linear_bandit.py:54-97, DPT sampling
-    controller) over this rank's task block, then the regret mean / SEM curves over all tasks."""
+    controller) over this rank's task block, then the regret mean / SEM curves over all tasks.
+    keep_last: the dict's "last" holds what the latest step returned, the regret curves and the
+    rollout's per-task actions, rewards and arm values (for --dump-outputs)."""
     import dpt_hip
     from dpt_hip.distributed import regret_stats_allreduce
     A, H = (5, H or 500) if wl == "bandit" else (20, H or 1000)
@@ -347,6 +377,7 @@ def bandit_workload(wl, L, H, var, first, count, n_total, rank):
         means_all = np.stack([arms @ t for t in thetas])
     means = torch.from_numpy(means_all[first:first + count]).cuda()
     opt = means.max(dim=1, keepdim=True).values  # the Opt controller's arm value (eval_bandit.py:123-128)
+    last = {}
 
     def one(step_idx, ev=None):
         if ev is not None:
@@ -356,7 +387,11 @@ def bandit_workload(wl, L, H, var, first, count, n_total, rank):
             ev[1].record()
         # the eval's output: suboptimality / cumulative-regret mean and SEM curves over all tasks
         # (evals/eval_bandit.py:169-178), from two all_reduces of 2 x H fp64 moments (RCCL for N>1)
-        return regret_stats_allreduce(opt, out["arm_value"], n_total)
+        stats = regret_stats_allreduce(opt, out["arm_value"], n_total)
+        if keep_last:  # the result tensors alone: the rollout's workspace is released as without it
+            last.clear()
+            last.update(stats, actions=out["actions"], rewards=out["rewards"], arm_value=out["arm_value"])
+        return stats
 
     def roofline(kern_ms, with_stream_ceiling=False):
         # kern_ms: HIP events around the one rollout launch (draws + rollout_bandit_kernel) on the
@@ -385,7 +420,8 @@ def bandit_workload(wl, L, H, var, first, count, n_total, rank):
     # rollout_bandit_kernel: fp32 VALU + v_mfma_f32_16x16x4_f32 products; env arithmetic fp64
     dtype = "f32 (model: VALU + f32 MFMA) / f64 (env, rewards)"
     return dict(one=one, roofline=roofline, env_steps=n_total * H, workload=workload, dtype=dtype,
-                cfg={"tasks_per_gpu": count, "horizon": H, "arms": A}, sd=sd, means_all=means_all, H=H, A=A)
+                cfg={"tasks_per_gpu": count, "horizon": H, "arms": A}, sd=sd, means_all=means_all, H=H, A=A,
+                last=last)
 
 
 def main():
@@ -398,11 +434,16 @@ def main():
     ap.add_argument("--H", type=int, default=None)
     ap.add_argument("--var", type=float, default=0.3)
     ap.add_argument("--layers", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines, the stream-ceiling "
+                         "probe, the DarkRoom roofline's replayed step, the DarkRoom and linear sub-objects")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-darkroom", action="store_true",
-                    help="bandit: skip the DarkRoom sub-object (darkroom_c3 / darkroom_c5_shard)")
+                    help="--full, bandit: skip the DarkRoom sub-object (darkroom_c3 / darkroom_c5_shard)")
     ap.add_argument("--no-linear", action="store_true",
-                    help="bandit: skip the linear_c4_shard sub-object (BASELINE config 4's per-GPU shard)")
+                    help="--full, bandit: skip the linear_c4_shard sub-object (BASELINE config 4's per-GPU shard)")
     ap.add_argument("--darkroom-memo", type=int, choices=(0, 1), default=1,
                     help="darkroom: 1 = one window forward per distinct state per episode, 0 = one per step")
     args = ap.parse_args()
@@ -427,23 +468,26 @@ def main():
     N, L, wl = args.tasks, args.layers, args.workload
     n_total = N * world
     first, count = shard(n_total, world, rank)
+    keep_last = args.dump_outputs is not None and rank == 0
     if wl in ("bandit", "linear"):
-        bw = bandit_workload(wl, L, args.H, args.var, first, count, n_total, rank)
+        bw = bandit_workload(wl, L, args.H, args.var, first, count, n_total, rank, keep_last)
         one, env_steps_per_step, workload, cfg, dtype = bw["one"], bw["env_steps"], bw["workload"], bw["cfg"], \
             bw["dtype"]
         sd, means_all, H, A = bw["sd"], bw["means_all"], bw["H"], bw["A"]
     else:
         H, Heps = args.H or 100, 40
-        dw = darkroom_workload(L, H, Heps, N, first, count, n_total, dist, args.darkroom_memo)
+        dw = darkroom_workload(L, H, Heps, N, first, count, n_total, dist, args.darkroom_memo, keep_last)
         one, env_steps_per_step, workload, cfg, dtype = dw["one"], dw["env_steps"], dw["workload"], dw["cfg"], \
             dw["dtype"]
 
     elapsed, kern_ms = run_timed(one, args.steps, args.warmup, dist, backend, wl in ("bandit", "linear"))
     value = env_steps_per_step * args.steps / elapsed
+    if keep_last:
+        dump_outputs(args.dump_outputs, (bw if wl in ("bandit", "linear") else dw)["last"])
     if wl in ("bandit", "linear"):
-        roof = bw["roofline"](kern_ms, with_stream_ceiling=rank == 0)
-    else:
-        roof = dw["roofline"](kern_ms)
+        roof = bw["roofline"](kern_ms, with_stream_ceiling=args.full and rank == 0)
+    else:  # its roofline replays a step to count the window forwards: a run of its own
+        roof = dw["roofline"](kern_ms) if args.full else None
     line = {
         "metric": "env-steps/sec/GPU (DPT policy in loop), 5-arm bandit H=500, 1/2/4/8 MI355X",
         "value": value,
@@ -460,10 +504,13 @@ def main():
         "config": dict(workload=workload, parallelism=f"task-sharded x{world}",
                        env_steps_per_step=env_steps_per_step, **cfg),
         "per_gpu_value": value / world,
-        "roofline": roof,
     }
+    if roof is not None:
+        line["roofline"] = roof
     if wl != "bandit":
         line["metric"] = f"env-steps/sec ({wl} workload; headline metric is --workload bandit)"
+    if not args.full:
+        args.no_cpu_baseline = args.no_darkroom = args.no_linear = True
     if rank == 0 and world == 1 and wl == "bandit" and not args.no_cpu_baseline:
         base, kv = cpu_baseline(sd, means_all, H, args.var, L, A)
         line["cpu_baseline"] = base

@@ -37,6 +37,8 @@ def main(tag):
     cp(f"{g}/gpu_tests.log", f"{p}/gpu_tests.log.txt")
     cp(f"{g}/smoke.log", f"{p}/smoke.log.txt")
     strip_drm(f"{g}/bench_{tag}.json", f"{p}/bench.json")
+    # the full bench line (bench.py --full), where scripts/gpu_evidence.sh writes it
+    strip_drm(os.path.join(ROOT, os.environ.get("BENCH_OUT", "bench_out"), f"bench_{tag}.json"), f"{p}/bench.json")
     strip_drm(f"{g}/logit_err_{tag}.json", f"{p}/dr_logit_error.json")
     # traces: per-kernel stats of the three workloads
     cp(f"{g}/prof_{tag}/trace/run_kernel_stats.csv", f"{p}/bandit_kernel_stats.csv")
