@@ -54,28 +54,19 @@ __device__ unsigned long long g_dr_last;
 // other workgroup's waves on the same SIMD (only issue order changes: bit-identical;
 // -0.9 % at config 3)
 #define DPT_TAIL_PRIO(p) __builtin_amdgcn_s_setprio(p)
-// The wave that runs the step's serial tail (ln_f, head, selection, env step) and the memo-hit
-// chain (on its lane 0, which keeps the episode's state and return in registers): the last MLP
-// wave, whose blocks are the fewest (blocks_of_wave gives the last waves the middle block or none)
-#ifndef DPT_TAIL_WAVE
-#define DPT_TAIL_WAVE 3
-#endif
 
 namespace dpt {
 
 constexpr int kDrA = 5;                     // DarkRoom actions
 constexpr int kDrF = 10;                    // token features 2*sd + A + 1
-#ifndef DPT_DR_MEMO_STATES
-#define DPT_DR_MEMO_STATES 128
-#endif
-constexpr int kMemoStates = DPT_DR_MEMO_STATES;  // logits memo rows (grids up to 11 x 11)
+constexpr int kMemoStates = 128;            // logits memo rows (grids up to 11 x 11)
+// The wave that runs the step's serial tail (ln_f, head, selection, env step) and the memo-hit
+// chain (on its lane 0, which keeps the episode's state and return in registers): the last MLP
+// wave, whose blocks are the fewest (blocks_of_wave gives the last waves the middle block or none)
+constexpr int kTailWave = 3, kTailTid = 64 * kTailWave;
 
-// DPT_DR_EMB_GLOBAL: the token embedding (10 x 32 floats, read by the episode prologue and the table-free
-// kernels' block-0 re-embedding) from global memory instead of the LDS parameter block (1.25 KB less LDS
-// per workgroup)
-#ifndef DPT_DR_EMB_GLOBAL
-#define DPT_DR_EMB_GLOBAL 0
-#endif
+// The model-level parameters after the per-layer ones in the LDS parameter block (the token embedding,
+// 10 x 32 floats, is read by the episode prologue and the table-free kernels' block-0 re-embedding)
 struct PTop {
     int lnf_g, lnf_b, head_w, head_b, emb_b, wpe0, emb_w, total;
     __host__ __device__ static PTop make(int L) {
@@ -87,7 +78,7 @@ struct PTop {
         t.head_b = o; o += 8;
         t.emb_b = o; o += kE;
         t.wpe0 = o; o += kE;
-        t.emb_w = o; o += DPT_DR_EMB_GLOBAL ? 0 : kDrF * kE;
+        t.emb_w = o; o += kDrF * kE;
         t.total = o;
         return t;
     }
@@ -102,19 +93,14 @@ struct DrGeom {
     static constexpr int kWsPerTask = 3 * kBlk * 64 * 8;  // [x | u | layer-0 partial o] per task
 };
 
-// DPT_DR_WG3 (default): the 4-wave workspace kernel at three workgroups per CU (<= 168 VGPRs, and the
-// score product's keys read from the values' token-major rows so that three workgroups' LDS fit the
-// CU: 35.6 KB + the parameter block).  The rollout is latency-bound per workgroup, so a third task
-// per CU is nearly free: config 3 235.8 -> 202.4 ms, bit-identical (A/B in one process per library).
-#ifndef DPT_DR_WG3
-#define DPT_DR_WG3 1
-#endif
-#ifndef DPT_DR_NW8_2
-#define DPT_DR_NW8_2 1
-#endif
-#ifndef DPT_DR_WG3_N
-#define DPT_DR_WG3_N 3
-#endif
+// The waves per SIMD each kernel is compiled for (__launch_bounds__' second argument; a workgroup
+// puts NW / 4 waves on each SIMD).  The 4-wave workspace kernel runs at three workgroups per CU
+// (<= 168 VGPRs, and the score product's keys read from the values' token-major rows so that three
+// workgroups' LDS fit the CU: 35.6 KB + the parameter block).  The rollout is latency-bound per
+// workgroup, so a third task per CU is nearly free: config 3 235.8 -> 202.4 ms, bit-identical (A/B
+// in one process per library).  The 4-wave workspace-free kernel and the 8-wave workspace kernel
+// run at two workgroups per CU, the others at one.
+constexpr int dr_waves_per_simd(bool kWs, int NW) { return NW == 4 ? (kWs ? 3 : 2) : (NW == 8 && kWs ? 4 : 1); }
 // 16-B multiple: the dynamic parameter block P follows it and is read with 16-B loads.
 // kWs (a per-task workspace is given): the layer-0 partials live in the workspace and
 // the freed LDS holds the values as split pair tiles (P V on mfma_x3);
@@ -122,9 +108,9 @@ struct DrGeom {
 template <bool kWs, int NW>
 struct alignas(16) DrSmem {
     static constexpr int kFwdT = DrGeom<NW>::kT, kFwdBlocks = DrGeom<NW>::kBlk;
-    // keys and values of the current layer (the 16-wave geometry reads the keys from the values'
-    // rows: 512 tokens of both in LDS)
-    KVBuf<kFwdT, kSplitKeys, kSplitKeys && kWs, kWs && (NW == 16 || (NW == 4 && DPT_DR_WG3) || (NW == 8 && DPT_DR_NW8_2))> kv;
+    // keys and values of the current layer (with the workspace one split image serves both: 512
+    // tokens of both in LDS at 16 waves, three workgroups per CU at 4)
+    KVBuf<kFwdT, true, kWs> kv;
     int2 ctx[kFwdT];   // context transitions, oldest first: .x = x|y<<8|a<<16|r<<24, .y = nx|ny<<8
     int2 cur[kFwdT];   // this episode's transitions
     // layer-0 episode cache: the causal softmax partial of every token over keys
@@ -181,18 +167,16 @@ struct DarkroomParams {
 // o is the layer-0 episode partial (the prologue's attention over keys 1..t).
 // The workspace starts with the per-state table (kDrTab floats), then the task caches, at the
 // stride of the launch's geometry (dpt_darkroom_workspace_numel_window).
-// DPT_DR_L0LIN (default): layer 0's attention output enters c_proj linearly.  Per token t the
+// Layer 0's attention output enters c_proj linearly.  Per token t the
 // merged output is o_t = (1 - a_t) o'_t + a_t v0 (o'_t: the episode's normalised partial over keys
 // 1..t, v0: the query token's value, a_t = 1 / (1 + l_t 2^(m_t - s0_t)), s0_t = q_t . k0), so
 //   x_t + c_proj(o_t) = A_t + a_t (V0 - C_t),  C_t = Wvp o'_t + bvp,  A_t = x_t + C_t,  V0 = Wvp v0 + bvp.
 // The episode prologue stores A and C in the workspace (slots x and o), the state table holds V0, and a
 // step's layer 0 is the score, one exp and one rcp per token and a packed sub + fma per value instead of
-// the merge, the split of o and c_proj's six MFMAs.  Same algebra, other fp32 rounding.
-#ifndef DPT_DR_L0LIN
-#define DPT_DR_L0LIN 1
-#endif
+// the merge, the split of o and c_proj's six MFMAs.  Same algebra, other fp32 rounding.  (The kernels
+// without the state table keep the merge.)
 // per state: [x | y | V0][g][8] (the query token's layer-0 input, its LN1 output, Wvp y + bvp)
-constexpr int kDrTabPerState = (DPT_DR_L0LIN ? 3 : 2) * 4 * 8;
+constexpr int kDrTabPerState = 3 * 4 * 8;
 constexpr int kDrTab = kMemoStates * kDrTabPerState;
 constexpr int kDrMaxWaves = 16;
 template <int NW>
@@ -213,9 +197,9 @@ __device__ inline void ws_load(const float* d, float (&v)[8]) {
     }
 }
 
-// DPT_DR_L0LIN episode prologue: c = Wvp o' + bvp from attend's (o, l) (o / l = o' x 2^attn_ey), at true
-// scale, and x += c (A); the token-0 column (no key in 1..0: l = 0) gets c = 0
-template <int NB, int J0 = 0>
+// The table kernels' episode prologue: c = Wvp o' + bvp from attend's (o, l) (o / l = o' x 2^attn_ey), at
+// true scale, and x += c (A); the token-0 column (no key in 1..0: l = 0) gets c = 0
+template <int NB>
 __device__ inline void l0_cproj(const float* W, const FragSrc3& f3, float (&o)[2][8], const float (&l)[2],
                                 float (&x)[2][8], const int (&qb)[2], const ModelView& M) {
     const int lane = lane_id(), g = lane >> 4;
@@ -224,7 +208,7 @@ __device__ inline void l0_cproj(const float* W, const FragSrc3& f3, float (&o)[2
     const floatx4 b0 = ld4(W + PL::proj_b + 4 * g), b1 = ld4(W + PL::proj_b + 16 + 4 * g);  // scaled (PL)
     const float down = exp2i(-(M.attn_ew + M.attn_ey));
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) {
+    for (int j = 0; j < NB; ++j) {
         const Split2 os = split2(o[j], l[j] > 0.f ? __builtin_amdgcn_rcpf(l[j]) : 0.f);
         const floatx4 c0 = mfma_x3(w0, os, b0), c1 = mfma_x3(w1, os, b1);
         const bool tok0 = qb[j] == 0 && (lane & 15) == 0;
@@ -314,7 +298,6 @@ __global__ void __launch_bounds__(64) state_tables_kernel(ModelView M, int dim, 
         ws_store(d, x);
         ws_store(d + 32, y);
     }
-#if DPT_DR_L0LIN
     // V0 = Wvp y + bvp (fp32 fma chain per feature), stored in the same [g][8] lane order
     __shared__ float ys[kE];
     if ((lane & 15) == 0) {
@@ -329,7 +312,6 @@ __global__ void __launch_bounds__(64) state_tables_kernel(ModelView M, int dim, 
         const int gf = (lane & 15) >> 2, kk = 4 * (lane >> 4) + (lane & 3);
         tab[(size_t)s * kDrTabPerState + 64 + gf * 8 + kk] = v;
     }
-#endif
 }
 
 // LDS stores of this wave visible to its own later loads (waits for them: no barrier, one wave)
@@ -341,14 +323,15 @@ __device__ inline void lds_wave_sync() {
 
 // Sum over the 32 lanes of each half of the wave (DPP within rows of 16, then the xor-16 partner);
 // every lane of the half gets the same value
+template <int kCtrl>
+__device__ inline float dr_dpp(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), kCtrl, 0xF, 0xF, false));
+}
 __device__ inline float dr_sum32(float d) {
-#define DR_DPP(v, ctrl) \
-    __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xF, 0xF, false))
-    d += DR_DPP(d, 0xB1);   // quad_perm xor 1
-    d += DR_DPP(d, 0x4E);   // quad_perm xor 2
-    d += DR_DPP(d, 0x141);  // row_half_mirror: the two quads of each 8
-    d += DR_DPP(d, 0x140);  // row_mirror: the two 8s of each row of 16
-#undef DR_DPP
+    d += dr_dpp<0xB1>(d);   // quad_perm xor 1
+    d += dr_dpp<0x4E>(d);   // quad_perm xor 2
+    d += dr_dpp<0x141>(d);  // row_half_mirror: the two quads of each 8
+    d += dr_dpp<0x140>(d);  // row_mirror: the two 8s of each row of 16
     return sum_x16(d);      // the two rows of each 32
 }
 
@@ -361,8 +344,7 @@ __device__ inline float dr_sum32(float d) {
 //    32 w .. 32 w + 31 of c_fc (unit 32 w + f, the half's 16 inputs, halves summed) + gelu_new, and
 //    their share of mlp.c_proj into feature f (the half's 16 units, halves summed) -> part_y[w];
 //  dr_tail_head (the tail wave, after a barrier): the four shares + residual, ln_f, head.
-// Each lane's 48 weights (pack_tail_kernel): Wvp and c_fc loaded before the attention partials, mlp.c_proj
-// after their barrier (dr_tail_ld_*).
+// Each lane's 48 weights (pack_tail_kernel) are loaded before the attention partials (dr_tail_ld_*).
 constexpr int kDrTailWv = 0, kDrTailFc = 64 * 16, kDrTailMp = 64 * 16 + 4 * 64 * 16,
               kDrTailFloats = 64 * 16 + 2 * 4 * 64 * 16;
 struct DrTailW {
@@ -493,18 +475,8 @@ __global__ void pack_tail_kernel(ModelView M, float* __restrict__ out) {
 // plain pairing.  Which wave computes a block changes no result (-2.2 % at config 3: the 7 blocks
 // of a 101-token window on 4 waves had wave 0 holding blocks 0 and 6 with the key-tile tail,
 // wave 3 the single block 3).  Returns the wave's block count.
-// DPT_DR_SHORT8 (experimental): windows of up to 128 tokens on the 8-wave geometry, one block per
-// wave (two workgroups per CU) instead of the 4-wave one with two blocks per wave (three per CU)
-#ifndef DPT_DR_SHORT8
-#define DPT_DR_SHORT8 0
-#endif
 template <int NW>
 __device__ inline int assign_blocks(int wave, int nqb, int (&qb)[2]) {
-    if (DPT_DR_SHORT8 && NW == 8 && nqb <= NW) {
-        qb[0] = wave;
-        qb[1] = wave;
-        return wave < nqb ? 1 : 0;
-    }
     if (nqb < 2 * NW) {
         if (wave == NW - 1) {
             qb[0] = nqb - 1;
@@ -521,65 +493,36 @@ __device__ inline int assign_blocks(int wave, int nqb, int (&qb)[2]) {
 // them out of the step loop, and at the 106-SGPR limit they live as spills in VGPR lanes, read back
 // by v_readlane (a VALU instruction plus its hazard wait) at every use.  Recomputing them is a few
 // scalar instructions.
-#ifndef DPT_DR_OPAQUE
-#define DPT_DR_OPAQUE 1
-#endif
 #define DR_OPQ(v) asm volatile("" : "+s"(v))
-#ifndef DPT_DR_SEQ_BLOCKS
-#define DPT_DR_SEQ_BLOCKS 0
-#endif
-#ifndef DPT_DR_SEQ4
-#define DPT_DR_SEQ4 0
-#endif
-#ifndef DPT_DR_HIT_WAVE
-#define DPT_DR_HIT_WAVE 1
-#endif
 // one phase over the wave's blocks inside the step: specialised on NBC when it is known at compile
-// time (no-op for 0), else dispatched on the run-time count (DPT_BLOCKS)
-// With kSeqBlocks (DPT_DR_SEQ_BLOCKS = 1; the 8- and 16-wave geometries, 128 VGPRs per wave) a
-// two-block wave runs each phase for one block after the other (NB = 1 at slots J0 = 0 and 1): the
-// same arithmetic per block, so the same results (tested bit-identical), with one block's products
-// and split operands live at a time instead of two.  It cuts their scratch from 64 to 16 B/lane but
-// is 3.7 % slower at window 201 and 6 % at 301 (profiles/r6/ab_seq_blocks.json): the two blocks'
-// interleaved chains hide each other's latency, which the spills cost less than.  Off by default.
-#define DR_BLOCKS(...)                                      \
-    do {                                                    \
-        if constexpr (NBC >= 0) {                           \
-            if constexpr (NBC == 2 && kSeqBlocks) {         \
-                {                                           \
-                    constexpr int NB = 1, J0 = 0;           \
-                    __VA_ARGS__;                            \
-                }                                           \
-                {                                           \
-                    constexpr int NB = 1, J0 = 1;           \
-                    __VA_ARGS__;                            \
-                }                                           \
-            } else if constexpr (NBC > 0) {                 \
-                constexpr int NB = NBC, J0 = 0;             \
-                __VA_ARGS__;                                \
-            }                                               \
-        } else {                                            \
-            DPT_BLOCKS(nb, __VA_ARGS__);                    \
-        }                                                   \
+// time (no-op for 0), else dispatched on the run-time count (DPT_BLOCKS: the workspace-free prologue).
+// A two-block wave runs each phase for both blocks together.  (One block after the other, with one
+// block's products and split operands live at a time, was tried for the 8- and 16-wave geometries
+// at 128 VGPRs per wave: it cut their scratch from 64 to 16 B/lane but was 3.7 % slower at window
+// 201 and 6 % at 301, profiles/r6/ab_seq_blocks.json: the two blocks' interleaved chains hide each
+// other's latency, which the spills cost less than.)
+#define DR_BLOCKS(...)                   \
+    do {                                 \
+        if constexpr (NBC > 0) {         \
+            constexpr int NB = NBC;      \
+            __VA_ARGS__;                 \
+        } else if constexpr (NBC < 0) {  \
+            DPT_BLOCKS(nb, __VA_ARGS__); \
+        }                                \
     } while (0)
-
 
 // kTab: token 0's layer-0 input and LN1 output come from the per-state table (the workspace kernels
 // on grids of <= kMemoStates cells); without it block 0 is re-embedded and normalised every step
 template <bool kWs, int NW, bool kTab = kWs>
-__global__ void __launch_bounds__(NW * 64, NW == 4 ? (kWs && DPT_DR_WG3 ? DPT_DR_WG3_N : 2) : (NW == 8 && kWs && DPT_DR_NW8_2 ? 4 : 1))
+__global__ void __launch_bounds__(NW * 64, dr_waves_per_simd(kWs, NW))
 rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
     static_assert(kWs || !kTab, "the state table lives in the workspace");
-    constexpr bool kSeqBlocks = (DPT_DR_SEQ_BLOCKS && NW >= 8) || (DPT_DR_SEQ4 && NW == 4);  // DR_BLOCKS
-    // with kSeqBlocks the last layer's fp32 tail weights load after the partials' barrier
-    constexpr bool kTailLate = kSeqBlocks;
     __shared__ DrSmem<kWs, NW> S;
     constexpr bool kSplitV = decltype(S.kv)::kSplitV;
     extern __shared__ float P[];
     const int task = blockIdx.x;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int kTailWave = DPT_TAIL_WAVE, kTailTid = 64 * kTailWave;
     static_assert(kTailWave < NW, "the tail wave is a wave of the workgroup");
     const int steps_total = p.Heps * p.horizon;
     const float scale = 0.17677669529663687f;  // 1/sqrt(head_dim = 32)
@@ -599,14 +542,9 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
     if constexpr (kSplitV) {  // finite values in tiles no episode has written yet (attend)
         uint4* vs = reinterpret_cast<uint4*>(&S.kv.VT[0][0][0]);
         for (int i = tid; i < (int)(sizeof(S.kv.VT) / 16); i += blockDim.x) vs[i] = uint4{0u, 0u, 0u, 0u};
-        if constexpr (decltype(S.kv)::kKS) {  // the key tiles too: attend scores the tile past the diagonal
-            uint4* ks = reinterpret_cast<uint4*>(&S.kv.KS[0][0][0]);
-            for (int i = tid; i < (int)(sizeof(S.kv.KS) / 16); i += blockDim.x) ks[i] = uint4{0u, 0u, 0u, 0u};
-        }
     }
-    if (!DPT_DR_EMB_GLOBAL)
-        for (int i = tid; i < kDrF * kE; i += blockDim.x) P[pt.emb_w + i] = M.emb_w[i];
-    const float* embw = DPT_DR_EMB_GLOBAL ? M.emb_w : P + pt.emb_w;
+    for (int i = tid; i < kDrF * kE; i += blockDim.x) P[pt.emb_w + i] = M.emb_w[i];
+    const float* embw = P + pt.emb_w;
     diag_bias_init(S.diag_bias, tid, blockDim.x);
     const float* diag_bias = S.diag_bias;
 
@@ -624,10 +562,6 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
         const int nqb = (T + 15) >> 4;
         int qb[2];
         const int nb = assign_blocks<NW>(wave, nqb, qb);
-#if !DPT_DR_OPAQUE
-        const int qlast = (T - 1) >> 4, clast = (T - 1) & 15;
-        const bool own0 = nb > 0 && qb[0] == 0;
-#endif
         if (tid == 0) {
             S.sx = 0;
             S.sy = 0;
@@ -663,17 +597,16 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
                 if (j < NBR) embed_block(S, P, pt, embw, M.wpe, qb[j], T, x[j]);
-            DR_BLOCKS((ln_n<NB, J0>(x, xn, P + PL::ln1_g, P + PL::ln1_b), u_proj_kv3_n<NB, J0>(P, split0, xn, q, S.kv, qb, M)));
+            DR_BLOCKS((ln_n<NB>(x, xn, P + PL::ln1_g, P + PL::ln1_b), u_proj_kv3_n<NB>(P, split0, xn, q, S.kv, qb, M)));
             if constexpr (kWs) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     if (j >= NBR) break;
-                    if (!(DPT_DR_L0LIN && kTab)) ws_store(l0_cache<NW>(p, task, 0, qb[j]), x[j]);
+                    if constexpr (!kTab) ws_store(l0_cache<NW>(p, task, 0, qb[j]), x[j]);
                     ws_store(l0_cache<NW>(p, task, 1, qb[j]), q[j]);
                 }
             }
             bar_lds();
-#if DPT_DR_L0LIN
             if constexpr (kTab) {
                 // the partials through c_proj once per episode: C = Wvp o' + bvp, A = x + C (the token-0
                 // column has no partial: C = 0 there, and its A comes from the state table)
@@ -689,7 +622,7 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                         S.l0l[qb[j] * 16 + lane] = l[j] * exp2i(-kPExp);
                     }
                 }
-                DR_BLOCKS(l0_cproj<NB, J0>(P, split0, o, l, x, qb, M));
+                DR_BLOCKS(l0_cproj<NB>(P, split0, o, l, x, qb, M));
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     if (j >= NBR) break;
@@ -699,7 +632,6 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                 __syncthreads();
                 return;
             }
-#endif
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 if (j >= NBR) break;
@@ -758,7 +690,7 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
             }
         };
         for (int t = 0; t < p.horizon; ++t) {
-            if (DPT_DR_HIT_WAVE && p.memo && p.sample) {
+            if (p.memo && p.sample) {
                 // the tail wave runs consecutive steps whose state was already queried this episode
                 // (a memo hit needs no forward) as one wave-uniform chain: lane k < 5 reads the row's
                 // cdf value q_k (and lanes 6..10 its logits) in one LDS round trip, the five compares
@@ -827,9 +759,9 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                 t = S.tnext;
                 if (t >= p.horizon) break;
             } else if (p.memo) {
-                // thread 0 runs consecutive steps whose state was already queried this
-                // episode (a memo hit needs no forward); the other threads wait at one
-                // barrier for the first state that needs one
+                // greedy selection: the tail wave's lane 0 alone runs consecutive steps whose state
+                // was already queried this episode (a memo hit needs no forward); the other threads
+                // wait at one barrier for the first state that needs one
                 if (tid == kTailTid) {
                     DPT_TAIL_PRIO(3);  // the memo-hit chain is the workgroup's critical path
                     int tt = t;
@@ -855,8 +787,8 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                 t = S.tnext;
                 if (t >= p.horizon) break;
             }
-#if DPT_DR_OPAQUE
-            // per-step copies of the episode's block assignment (see DR_OPQ)
+            // per-step copies of the episode's block assignment (see DR_OPQ): the step's forward reads
+            // these qb, nb, T and task, which shadow the episode's
             int wv = wave, Tq = T, task_s = task;
             DR_OPQ(wv);
             DR_OPQ(Tq);
@@ -868,14 +800,11 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
             const int qlast = (Tq - 1) >> 4, clast = (Tq - 1) & 15;
             const int task = task_s;
             const int T = Tq;
-#endif
             // The window forward of this step, specialised on the wave's block count (2, 1 or 0):
             // one dispatch per step instead of a branch per phase, so no register copies merge the
             // two paths' activations after every phase
             auto forward = [&](auto nb_c) {
-                // NBC = the wave's block count, or -1: taken at run time (each phase dispatches)
-                constexpr int NBC = decltype(nb_c)::value;
-                const int NBR = NBC >= 0 ? NBC : nb;
+                constexpr int NBC = decltype(nb_c)::value, NBR = NBC;  // the wave's block count
                 float x[2][8];
                 float q[2][8];
                 const int sx = S.sx, sy = S.sy;
@@ -910,7 +839,7 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                         if constexpr (kWs) {
                             if (own0) ln_n<1>(x, xn, P + PL::ln1_g, P + PL::ln1_b);
                         } else {
-                            DR_BLOCKS(ln_n<NB, J0>(x, xn, P + PL::ln1_g, P + PL::ln1_b));
+                            DR_BLOCKS(ln_n<NB>(x, xn, P + PL::ln1_g, P + PL::ln1_b));
                         }
                         if (own0) {  // block 0: key/value (= y) of the query token (the merge below reads them)
                             const int lane = lane_id();
@@ -926,13 +855,14 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                         }
                         // the queries after the store above: no branch between their MFMAs and the
                         // first reads of q (the wait states stay in one block: attend's note)
-                        if constexpr (!kWs) DR_BLOCKS(u_proj3_n<NB, J0>(P, split0, xn, q, M));
+                        if constexpr (!kWs) DR_BLOCKS(u_proj3_n<NB>(P, split0, xn, q, M));
                         bar_lds();
                     }
                     DR_STAMP(0);
-#if DPT_DR_L0LIN
-                    if (kTab && NBR > 0) {
-                        // x = A + a (V0 - C) per token column (DPT_DR_L0LIN): x holds A, the workspace's o slot C
+                    // (NBR > 0: for a wave without blocks either form would still leave its opaque
+                    // lane_id() in the code)
+                    if constexpr (kTab && NBR > 0) {
+                        // x = A + a (V0 - C) per token column: x holds A, the workspace's o slot C
                         const int lane = lane_id(), g = lane >> 4;
                         const float* tr = p.tab + (size_t)(sx * p.dim + sy) * kDrTabPerState + 8 * g;
                         const floatx4 ka = ld4(tr + 32), kc = ld4(tr + 36);
@@ -978,26 +908,13 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                             }
                         }
                         float xn[2][8];
-                        DR_BLOCKS((ln_n<NB, J0>(x, xn, P + PL::ln2_g, P + PL::ln2_b),
-                                   mlp3_n<NB, J0>(P, split0, xn, x, M.mlp_ew, M.mlp_ex)));
-                    } else
-#endif
-                    if (NBR > 0) {
+                        DR_BLOCKS((ln_n<NB>(x, xn, P + PL::ln2_g, P + PL::ln2_b),
+                                   mlp3_n<NB>(P, split0, xn, x, M.mlp_ew, M.mlp_ex)));
+                    } else if constexpr (NBR > 0) {
                         // merge key 0 into the cached partial of every token column
                         const int lane = lane_id(), g = lane >> 4;
-                        floatx4 ka, kc, va, vb;
-                        if constexpr (kTab) {
-                            const float* y0 = p.tab + (size_t)(sx * p.dim + sy) * kDrTabPerState + 32 + 8 * g;
-                            ka = ld4(y0);
-                            kc = ld4(y0 + 4);
-                            va = ka;
-                            vb = kc;
-                        } else {
-                            ka = ld4(&S.k0[4 * g]);
-                            kc = ld4(&S.k0[16 + 4 * g]);
-                            va = ld4(&S.v0[4 * g]);
-                            vb = ld4(&S.v0[16 + 4 * g]);
-                        }
+                        const floatx4 ka = ld4(&S.k0[4 * g]), kc = ld4(&S.k0[16 + 4 * g]);
+                        const floatx4 va = ld4(&S.v0[4 * g]), vb = ld4(&S.v0[16 + 4 * g]);
                         float o[2][8], sd[2] = {0.f, 0.f};
     #pragma unroll
                         for (int j = 0; j < 2; ++j) {
@@ -1050,42 +967,26 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                         }
                         float xn[2][8];
                         // o is the attention output x 2^attn_ey already (the merge's inv)
-    #ifndef DPT_DR_SKIP_MLP  // (timing-only diagnostic builds: DPT_DR_SKIP_* leave phases out; results wrong)
-                        DR_BLOCKS((attn_proj3<NB, J0>(P, split0, o, x, M, 1.0f), ln_n<NB, J0>(x, xn, P + PL::ln2_g, P + PL::ln2_b),
-                                       mlp3_n<NB, J0>(P, split0, xn, x, M.mlp_ew, M.mlp_ex)));
-    #else
-                        DR_BLOCKS(attn_proj3<NB, J0>(P, split0, o, x, M, 1.0f));
-    #endif
+                        DR_BLOCKS((attn_proj3<NB>(P, split0, o, x, M, 1.0f), ln_n<NB>(x, xn, P + PL::ln2_g, P + PL::ln2_b),
+                                   mlp3_n<NB>(P, split0, xn, x, M.mlp_ew, M.mlp_ex)));
                     }
                     DR_STAMP(1);
                 }
 
-// DPT_DR_TAIL_LD_EARLY: the MLP waves' 48 fp32 tail weights per lane issued before the last layer's
-// attention partials (1, the default: no spill at the 168-VGPR bound, -0.8 % at config 3,
-// profiles/r5e/ab_darkroom_tail_ld_early.json), at the start of the last layer (2: 128 B/lane of
-// spill) or after the partials' barrier (0)
-#ifndef DPT_DR_TAIL_LD_EARLY
-#define DPT_DR_TAIL_LD_EARLY 1
-#endif
                 DrTailW tlw;  // the last block's fp32 tail weights (dr_tail_ld_*)
                 for (int layer = 1; layer < L; ++layer) {
                     const bool last = layer == L - 1;
-                    if (DPT_DR_TAIL_LD_EARLY == 2 && !kTailLate && last && wave < kFF / 32) {  // in flight across the last layer
-                        const float* tw0 = p.frag + (size_t)L * (Frag3::bytes / 4);
-                        dr_tail_ld_early(tw0, wave, tlw);
-                        dr_tail_ld_late(tw0, wave, tlw);
-                    }
                     auto& kv = S.kv;
                     const float* W = P + layer * PL::size;
                     float q[2][8];
                     {
                         float xn[2][8];
                         if (!last) {
-                            DR_BLOCKS((ln_n<NB, J0>(x, xn, W + PL::ln1_g, W + PL::ln1_b),
-                                           u_proj_kv3_n<NB, J0>(W, split0.layer(layer), xn, q, kv, qb, M)));
+                            DR_BLOCKS((ln_n<NB>(x, xn, W + PL::ln1_g, W + PL::ln1_b),
+                                       u_proj_kv3_n<NB>(W, split0.layer(layer), xn, q, kv, qb, M)));
                         } else {
                             // the last layer needs q only for token T-1 (block qlast)
-                            DR_BLOCKS((ln_n<NB, J0>(x, xn, W + PL::ln1_g, W + PL::ln1_b), kv_from_y<NB, J0>(kv, qb, xn, M)));
+                            DR_BLOCKS((ln_n<NB>(x, xn, W + PL::ln1_g, W + PL::ln1_b), kv_from_y<NB>(kv, qb, xn, M)));
     #pragma unroll
                             for (int j = 0; j < 2; ++j) {
                                 if (j < NBR && qb[j] == qlast) {
@@ -1109,7 +1010,6 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                     bar_lds();
                     DR_STAMP(2 * layer);
                     if (last) break;
-    #ifndef DPT_DR_SKIP_ATTN
                     if (NBR > 0) {
                         float o[2][8], l[2];
                         if constexpr (NBC == 2 && kSplitV) {  // the two blocks' l reduced together (sum_cols2)
@@ -1127,18 +1027,15 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                                 attend(kv, q[j], qb[j], 0, scale, m, l[j], o[j], M, diag_bias);
                             }
                         }
-                        DR_BLOCKS(attn_proj3_ol<NB, J0>(W, split0.layer(layer), o, l, x, M));
+                        DR_BLOCKS(attn_proj3_ol<NB>(W, split0.layer(layer), o, l, x, M));
                     }
-    #endif
                     bar_lds();  // every read of this layer's K/V is done
                     DR_STAMP(2 * layer + 1);
-    #ifndef DPT_DR_SKIP_MLP
                     {
                         float xn[2][8];
-                        DR_BLOCKS((ln_n<NB, J0>(x, xn, W + PL::ln2_g, W + PL::ln2_b),
-                                       mlp3_n<NB, J0>(W, split0.layer(layer), xn, x, M.mlp_ew, M.mlp_ex)));
+                        DR_BLOCKS((ln_n<NB>(x, xn, W + PL::ln2_g, W + PL::ln2_b),
+                                   mlp3_n<NB>(W, split0.layer(layer), xn, x, M.mlp_ew, M.mlp_ex)));
                     }
-    #endif
                 }
 
                 // ---- last layer for the one token T-1, spread over the waves.  Every
@@ -1147,11 +1044,14 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                     const float* W = P + (L - 1) * PL::size;
                     const auto& kv = S.kv;
                     // the fp32 tail weights of the last block (pack_tail_kernel): each MLP wave's 48 per
-                    // lane, in flight across the attention partials and their barrier
+                    // lane, in flight across the attention partials and their barrier (no spill at the
+                    // 168-VGPR bound, -0.8 % at config 3 against loading them after the barrier,
+                    // profiles/r5e/ab_darkroom_tail_ld_early.json; from the start of the last layer they
+                    // cost 128 B/lane of spill)
                     constexpr int kMlpWaves = kFF / 32;
                     static_assert(kMlpWaves == 4 && NW >= kMlpWaves && kTailWave < kMlpWaves, "four MLP waves");
                     const float* tw = p.frag + (size_t)L * (Frag3::bytes / 4);
-                    if (DPT_DR_TAIL_LD_EARLY == 1 && !kTailLate && wave < kMlpWaves) {  // in flight across the attention partials
+                    if (wave < kMlpWaves) {
                         dr_tail_ld_early(tw, wave, tlw);
                         dr_tail_ld_late(tw, wave, tlw);
                     }
@@ -1253,25 +1153,15 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                     // matrix-vector products (dr_tail_mlp); (3) after a barrier the tail wave: ln_f, head,
                     // selection and the env step
                     float x1 = 0.f;
-                    if (wave < kMlpWaves) {
-                        if (!DPT_DR_TAIL_LD_EARLY || kTailLate) {  // (the 128-VGPR geometries: after the barrier)
-                            dr_tail_ld_early(tw, wave, tlw);
-                            dr_tail_ld_late(tw, wave, tlw);
-                        }
-    #ifndef DPT_DR_SKIP_TAIL
-                        x1 = dr_tail_mlp(S, W, tlw, wave, nparts, M);
-    #endif
-                    }
+                    if (wave < kMlpWaves) x1 = dr_tail_mlp(S, W, tlw, wave, nparts, M);
                     bar_lds();
                     DR_STAMP(2 * L);
                     if (wave == kTailWave) {
                         // the step's serial tail: issue ahead of the other workgroup's waves on this SIMD
                         DPT_TAIL_PRIO(3);
                         const int lane = lane_id();
-                        float lg[kDrA] = {};
-    #ifndef DPT_DR_SKIP_TAIL
+                        float lg[kDrA];
                         dr_tail_head(S, P, W, pt, x1, M, lg);
-    #endif
                         DR_STAMP(2 * L + 2);
                         if (lane == 0) {
                             float q[kDrA] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -1294,18 +1184,9 @@ rollout_darkroom_kernel(ModelView M, DarkroomParams p) {
                     }
                 }
             };
-            // specialised on the wave's block count (DPT_DR_SPEC_NOWS = 0: the workspace-free kernels
-            // dispatch per phase instead, the A/B and diagnostic form, scripts/dr_nows_check.py)
-#ifndef DPT_DR_SPEC_NOWS
-#define DPT_DR_SPEC_NOWS 1
-#endif
-            if constexpr (kWs || DPT_DR_SPEC_NOWS) {
-                if (nb == 2) forward(std::integral_constant<int, 2>{});
-                else if (nb == 1) forward(std::integral_constant<int, 1>{});
-                else forward(std::integral_constant<int, 0>{});
-            } else {
-                forward(std::integral_constant<int, -1>{});
-            }
+            if (nb == 2) forward(std::integral_constant<int, 2>{});
+            else if (nb == 1) forward(std::integral_constant<int, 1>{});
+            else forward(std::integral_constant<int, 0>{});
             // the end of the step (with the memo, the barrier after the memo-hit chain at the top of
             // the loop would order the state and the partials as well, but dropping this one was
             // 1 % slower at config 3)
@@ -1446,10 +1327,8 @@ int launch_rollout_darkroom(const ModelView& M, const float* frag, const dpt_dar
     // keys and values of 512 tokens in LDS) up to 512
     const int64_t window = 1 + (int64_t)a.ctx_episodes * a.horizon;
     const bool ws = p.ws != nullptr;
-    if (window <= DrGeom<4>::kT) {
-        if (DPT_DR_SHORT8 && ws && p.tab) return launch_darkroom_geom<true, 8>(M, p, st);
+    if (window <= DrGeom<4>::kT)
         return ws ? launch_darkroom_geom<true, 4>(M, p, st) : launch_darkroom_geom<false, 4>(M, p, st);
-    }
     if (window <= DrGeom<8>::kT)
         return ws ? launch_darkroom_geom<true, 8>(M, p, st) : launch_darkroom_geom<false, 8>(M, p, st);
     if (!ws) {
@@ -1464,7 +1343,7 @@ int darkroom_max_window() { return DrGeom<kDrMaxWaves>::kT; }
 
 // per task: the stride of the geometry that runs the window (launch_rollout_darkroom's choice)
 int64_t darkroom_workspace_numel(int N, int64_t window) {
-    const int64_t per = window <= DrGeom<4>::kT ? (DPT_DR_SHORT8 ? DrGeom<8>::kWsPerTask : DrGeom<4>::kWsPerTask)
+    const int64_t per = window <= DrGeom<4>::kT   ? DrGeom<4>::kWsPerTask
                         : window <= DrGeom<8>::kT ? DrGeom<8>::kWsPerTask
                                                   : DrGeom<kDrMaxWaves>::kWsPerTask;
     return kDrTab + (int64_t)N * per;

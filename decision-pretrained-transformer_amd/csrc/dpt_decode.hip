@@ -56,10 +56,7 @@ namespace dpt {
 constexpr int kM = 16;                    // MFMA rows = task slots in LDS (TILE <= 16 are live)
 constexpr int kLdE = kE + 2;              // padded LDS row strides (conflict-free A reads)
 constexpr int kRows = 4;                  // K/V rows (of 8 positions) in flight per wave
-#ifndef DPT_YROWS
-#define DPT_YROWS 8
-#endif
-constexpr int kYRows = DPT_YROWS;         // y rows in flight per wave (rollout blocks >= 1; 8: -1.5 % vs 4)
+constexpr int kYRows = 8;                 // y rows in flight per wave (rollout blocks >= 1; 8: -1.5 % vs 4)
 constexpr int kChunks = kFF / 16;         // hidden-unit chunks of the fused c_fc -> mlp.c_proj
 #ifndef DPT_DEFAULT_CACHE_BUDGET
 #define DPT_DEFAULT_CACHE_BUDGET (224ll << 20)

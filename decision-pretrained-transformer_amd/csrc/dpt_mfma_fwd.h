@@ -27,32 +27,34 @@ struct PL {
 };
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
 // This workgroup's keys and values of the current layer, for windows of up to TMAX
-// tokens.  Keys are either fp32 token-major (K) or, with SPLITK, the fp16 two-part A
-// operand tiles of the score product (KS[block][part h|m][lane], y x 2^attn_ey, written
-// once by the lane that computed the key: 2 KB per 16 keys, no split per read).  Values
-// stay fp32 feature-major (Vt).
+// tokens, in one of three shapes:
+//  * plain (the prefill): keys fp32 token-major (K), values fp32 feature-major (Vt);
+//  * SPLITK (the workspace-free DarkRoom rollout): the keys as the fp16 two-part A operand tiles
+//    of the score product (KS[block][part h|m][lane], y x 2^attn_ey, written once by the lane
+//    that computed the key: 2 KB per 16 keys, no split per read), values still Vt;
+//  * SPLITK and SPLITV (the workspace DarkRoom rollout): one token-major split image VT that
+//    serves both the values and the keys; neither KS nor Vt is kept.
 // With SPLITV (requires SPLITK) the values are kept as the fp16 two-part split of y x 2^attn_ey
 // (the keys' split), token-major: VT[part h|m][key][kVTRow] (features 0..31, rows padded to 72 B).
 // The writer lane holds two runs of 4 consecutive features of its token (C-layout) and
 // stores each as one 8-B write; the A operand of O^T += V^T P^T over a pair of key tiles
 // (element j of lane (g, c) = V[key 16 (2 pair + (j >> 2)) + 4g + (j & 3)][feature 16 half + c],
 // the lane group's k order of P^T's C-layout over the two tiles) is read back transposed by
-// two ds_read_b64_tr_b16 per part (vt_split).  With KEYS_VT (requires SPLITV) the score product's
-// key tiles are read from the same rows too (key_split) and KS is not kept: half the LDS, for the
-// 512-token windows; otherwise the keys keep their own pre-split tiles (one 16-B read per part).
+// two ds_read_b64_tr_b16 per part (vt_split).  The score product's key tiles are read from the
+// same rows (key_split) and KS is not kept: half the LDS, which is what fits the 512-token windows
+// and three 4-wave workgroups per CU; without SPLITV the keys keep their own pre-split tiles (one
+// 16-B read per part).
 constexpr int kVTRow = kE + 4;  // halves per VT row: 72 B (8-B aligned rows for the transposed read)
-template <int TMAX, bool SPLITK = false, bool SPLITV = false, bool KEYS_VT = false>
+template <int TMAX, bool SPLITK = false, bool SPLITV = false>
 struct KVBuf {
     static_assert(SPLITK || !SPLITV, "split values need split keys");
-    static_assert(SPLITV || !KEYS_VT, "keys from VT need split values");
-    static constexpr bool kSplitK = SPLITK, kSplitV = SPLITV, kKeysVT = KEYS_VT;
-    static constexpr bool kKS = SPLITK && !KEYS_VT;
+    static constexpr bool kSplitK = SPLITK, kSplitV = SPLITV;
+    static constexpr bool kKS = SPLITK && !SPLITV;
     float K[SPLITK ? 1 : TMAX][kKStride];
     halfx8 KS[kKS ? TMAX / 16 : 1][kKS ? 2 : 1][kKS ? 64 : 1];  // (16 B when unused)
     _Float16 VT[SPLITV ? 2 : 1][SPLITV ? TMAX : 1][SPLITV ? kVTRow : 8];
     float Vt[SPLITV ? 1 : kE][TMAX + 4];
 };
-constexpr bool kSplitKeys = true;  // scores on mfma_x3 (and, with SPLITV, P V too)
 
 __device__ inline floatx4 mfma4(float a, float b, floatx4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -141,12 +143,12 @@ __device__ inline Split2 vt_split(const KV& S, int pp, int half, int lo) {
 }
 // The split A operand of the score product S^T = K Q^T for key tile kt: lane (g, c) holds the
 // k-elements j of key 16 kt + c, features 16 (j >> 2) + 4g + (j & 3) (the writer's C-layout order).
-// With KEYS_VT the keys are read from the token-major VT image (two 8-B runs of a row per part,
-// one ds_read2_b64; rows 72 B apart put the 16 lanes of a group on distinct banks), otherwise
+// With split values the keys are read from the token-major VT image (two 8-B runs of a row per
+// part, one ds_read2_b64; rows 72 B apart put the 16 lanes of a group on distinct banks), otherwise
 // from the pre-split key tiles KS.
 template <class KV>
 __device__ inline Split2 key_split(const KV& S, int kt, int lane) {
-    if constexpr (KV::kKeysVT) {
+    if constexpr (KV::kSplitV) {
         const int row = 16 * kt + (lane & 15), g = lane >> 4;
         const uint2* h = reinterpret_cast<const uint2*>(&S.VT[0][row][4 * g]);
         const uint2* m = reinterpret_cast<const uint2*>(&S.VT[1][row][4 * g]);
@@ -372,14 +374,13 @@ __device__ inline Split2 gelu_split(const floatx4& a, const floatx4& b, const Ge
                   __builtin_bit_cast(halfx8, uint4{mm[0], mm[1], mm[2], mm[3]})};
 }
 
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void ln_n(const float (&x)[2][8], float (&xn)[2][8], const float* gam, const float* bet) {
-    static_assert(NB == 1 || J0 == 0, "two blocks start at slot 0");
     if constexpr (NB == 2) {
         ln_cols2(x, xn, gam, bet);
     } else {
 #pragma unroll
-        for (int j = J0; j < J0 + NB; ++j) ln_cols(x[j], xn[j], gam, bet);
+        for (int j = 0; j < NB; ++j) ln_cols(x[j], xn[j], gam, bet);
     }
 }
 
@@ -402,7 +403,7 @@ __device__ inline void resid_add(float (&x)[8], const floatx4& a, const floatx4&
 // per pair of chunks (its K = 32 input is the two chunks' gelu outputs, C-layout).  Products
 // accumulate at scale 2^(mlp_ew + mlp_ex) (the biases enter scaled, exactly) and are scaled
 // back by the exact power of two.
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void mlp3_n(const float* W, const FragSrc3& f3, const float (&xn)[2][8], float (&x)[2][8],
                               int ew, int ex) {
     const int g = lane_id() >> 4;
@@ -417,7 +418,7 @@ __device__ inline void mlp3_n(const float* W, const FragSrc3& f3, const float (&
     Split2 wf0 = f3.ld2(Frag3::fc, vo), wf1 = f3.ld2(Frag3::fc + 1, vo);
     Split2 xs[2];
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) xs[j] = split2(xn[j], 1.0f);  // xn = ln_2 output x 2^mlp_ex (PL)
+    for (int j = 0; j < NB; ++j) xs[j] = split2(xn[j], 1.0f);  // xn = ln_2 output x 2^mlp_ex (PL)
 #pragma unroll
     for (int p = 0; p < kFF / 32; ++p) {
         const Split2 w0 = f3.ld2(Frag3::mp + p, vo), w1 = f3.ld2(Frag3::mp + 4 + p, vo);
@@ -425,27 +426,27 @@ __device__ inline void mlp3_n(const float* W, const FragSrc3& f3, const float (&
         const floatx4 fb0 = ld4(W + PL::fc_b + 2 * p * 16 + 4 * g);
         const floatx4 fb1 = ld4(W + PL::fc_b + (2 * p + 1) * 16 + 4 * g);
 #pragma unroll
-        for (int j = J0; j < J0 + NB; ++j)
+        for (int j = 0; j < NB; ++j)
             gs[j] = gelu_split(mfma_x3(wf0, xs[j], fb0), mfma_x3(wf1, xs[j], fb1), gk);
         if (p + 1 < kFF / 32) {
             wf0 = f3.ld2(Frag3::fc + 2 * p + 2, vo);
             wf1 = f3.ld2(Frag3::fc + 2 * p + 3, vo);
         }
 #pragma unroll
-        for (int j = J0; j < J0 + NB; ++j) {
+        for (int j = 0; j < NB; ++j) {
             y0[j] = mfma_x3(w0, gs[j], y0[j]);
             y1[j] = mfma_x3(w1, gs[j], y1[j]);
         }
     }
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) resid_add(x[j], y0[j], y1[j], down);
+    for (int j = 0; j < NB; ++j) resid_add(x[j], y0[j], y1[j], down);
 }
 
 // u = xn G + g0 of the NB blocks (the folded c_attn: only its q part) on fp16 two-part
 // products (mfma_x3) at scale 2^(attn_ew + attn_ey), returned at 2^attn_eq (the scale of the score
 // product's split query, so attend splits it as it stands); xs = the blocks' LayerNorm outputs
 // split at 2^attn_ey
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void u_proj3_w(const float* W, const Split2 (&wg)[2], const Split2 (&xs)[2], float (&q)[2][8],
                                  const ModelView& M) {
     const int g = lane_id() >> 4;
@@ -455,7 +456,7 @@ __device__ inline void u_proj3_w(const float* W, const Split2 (&wg)[2], const Sp
         const Split2& w = wg[ob];
         const floatx4 bias = ld4(W + PL::attn_b + ob * 16 + 4 * g);  // scaled (PL)
 #pragma unroll
-        for (int j = J0; j < J0 + NB; ++j) {
+        for (int j = 0; j < NB; ++j) {
             const floatx4 acc = mfma_x3(w, xs[j], bias) * down;
 #pragma unroll
             for (int r = 0; r < 4; ++r) q[j][ob * 4 + r] = acc[r];
@@ -468,41 +469,41 @@ __device__ inline void ld_g(const FragSrc3& f3, Split2 (&wg)[2]) {
     wg[0] = f3.ld2(Frag3::attn, vo);
     wg[1] = f3.ld2(Frag3::attn + 1, vo);
 }
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void u_proj3_s(const float* W, const FragSrc3& f3, const Split2 (&xs)[2], float (&q)[2][8],
                                  const ModelView& M) {
     Split2 wg[2];
     ld_g(f3, wg);
-    u_proj3_w<NB, J0>(W, wg, xs, q, M);
+    u_proj3_w<NB>(W, wg, xs, q, M);
 }
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void u_proj3_n(const float* W, const FragSrc3& f3, const float (&xn)[2][8], float (&q)[2][8],
                                  const ModelView& M) {
     Split2 xs[2];
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) xs[j] = split2(xn[j], 1.0f);  // xn = ln_1 output x 2^attn_ey (PL)
-    u_proj3_s<NB, J0>(W, f3, xs, q, M);
+    for (int j = 0; j < NB; ++j) xs[j] = split2(xn[j], 1.0f);  // xn = ln_1 output x 2^attn_ey (PL)
+    u_proj3_s<NB>(W, f3, xs, q, M);
 }
 
 // attn_proj on mfma_x3: x^T += Wvp^T o^T + bvp (o, a convex combination of the values y,
 // shares their bound and scale)
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void attn_proj3_w(const float* W, const Split2& w0, const Split2& w1, const Split2 (&os)[2],
                                     float (&x)[2][8], const ModelView& M) {
     const int g = lane_id() >> 4;
     const float down = exp2i(-(M.attn_ew + M.attn_ey));
     const floatx4 b0 = ld4(W + PL::proj_b + 4 * g), b1 = ld4(W + PL::proj_b + 16 + 4 * g);  // scaled (PL)
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) resid_add(x[j], mfma_x3(w0, os[j], b0), mfma_x3(w1, os[j], b1), down);
+    for (int j = 0; j < NB; ++j) resid_add(x[j], mfma_x3(w0, os[j], b0), mfma_x3(w1, os[j], b1), down);
 }
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void attn_proj3_s(const float* W, const FragSrc3& f3, const Split2 (&os)[2], float (&x)[2][8],
                                     const ModelView& M) {
     const int vo = FragSrc3::lane_off();
-    attn_proj3_w<NB, J0>(W, f3.ld2(Frag3::proj, vo), f3.ld2(Frag3::proj + 1, vo), os, x, M);
+    attn_proj3_w<NB>(W, f3.ld2(Frag3::proj, vo), f3.ld2(Frag3::proj + 1, vo), os, x, M);
 }
 // (oscale: the split's scale, 2^attn_ey for an attention output at its true scale)
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void attn_proj3(const float* W, const FragSrc3& f3, const float (&o)[2][8], float (&x)[2][8],
                                   const ModelView& M, float oscale) {
     // the Wvp tiles ahead of the split
@@ -510,21 +511,21 @@ __device__ inline void attn_proj3(const float* W, const FragSrc3& f3, const floa
     const Split2 w0 = f3.ld2(Frag3::proj, vo), w1 = f3.ld2(Frag3::proj + 1, vo);
     Split2 os[2];
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) os[j] = split2(o[j], oscale);
-    attn_proj3_w<NB, J0>(W, w0, w1, os, x, M);
+    for (int j = 0; j < NB; ++j) os[j] = split2(o[j], oscale);
+    attn_proj3_w<NB>(W, w0, w1, os, x, M);
 }
 // the same from attend's unnormalised (o, l): o / l is the attention output x 2^attn_ey already,
 // so the split takes 1 / l as its scale (one multiply per value; 1 / l by v_rcp_f32, 1 ulp, instead
 // of the dozen instructions of an IEEE division: -1.1 % at config 3 with the two below)
-template <int NB, int J0 = 0>
+template <int NB>
 __device__ inline void attn_proj3_ol(const float* W, const FragSrc3& f3, const float (&o)[2][8], const float (&l)[2],
                                      float (&x)[2][8], const ModelView& M) {
     const int vo = FragSrc3::lane_off();
     const Split2 w0 = f3.ld2(Frag3::proj, vo), w1 = f3.ld2(Frag3::proj + 1, vo);
     Split2 os[2];
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) os[j] = split2(o[j], __builtin_amdgcn_rcpf(l[j]));
-    attn_proj3_w<NB, J0>(W, w0, w1, os, x, M);
+    for (int j = 0; j < NB; ++j) os[j] = split2(o[j], __builtin_amdgcn_rcpf(l[j]));
+    attn_proj3_w<NB>(W, w0, w1, os, x, M);
 }
 
 // Folded attention input of the NB blocks qb[]: keys and values are the
@@ -532,29 +533,27 @@ __device__ inline void attn_proj3_ol(const float* W, const FragSrc3& f3, const f
 // C-layout of xn is the layout c_attn's K / V tiles had).  With split keys the
 // split of y at 2^attn_ey (xs, the lane's 8 values are its A-operand k-elements) is
 // what goes to LDS.
-template <int NB, int J0 = 0, class KV>
+template <int NB, class KV>
 __device__ inline void kv_store(KV& S, const int (&qb)[2], const float (&xn)[2][8], const Split2 (&xs)[2]) {
     const int lane = lane_id(), g = lane >> 4;
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) {
+    for (int j = 0; j < NB; ++j) {
         const int tok = qb[j] * 16 + (lane & 15);
-        if constexpr (KV::kSplitK) {
-            if constexpr (KV::kKS) {
-                S.KS[qb[j]][0][lane] = xs[j].h;
-                S.KS[qb[j]][1][lane] = xs[j].m;
-            }
-            if constexpr (KV::kSplitV) {
-                // the same split parts, token-major: value k of lane (g, c) is feature
-                // 16 (k >> 2) + 4g + (k & 3) of token 16 b + c, so each half of the lane's 8
-                // values is 4 consecutive features: one 8-B store per part and half
-                const uint4 hu = __builtin_bit_cast(uint4, xs[j].h), mu = __builtin_bit_cast(uint4, xs[j].m);
-                _Float16* row = &S.VT[0][tok][4 * g];
-                *reinterpret_cast<uint2*>(row) = uint2{hu.x, hu.y};
-                *reinterpret_cast<uint2*>(row + 16) = uint2{hu.z, hu.w};
-                _Float16* rowm = &S.VT[1][tok][4 * g];
-                *reinterpret_cast<uint2*>(rowm) = uint2{mu.x, mu.y};
-                *reinterpret_cast<uint2*>(rowm + 16) = uint2{mu.z, mu.w};
-            }
+        if constexpr (KV::kKS) {
+            S.KS[qb[j]][0][lane] = xs[j].h;
+            S.KS[qb[j]][1][lane] = xs[j].m;
+        }
+        if constexpr (KV::kSplitV) {
+            // the split parts token-major: value k of lane (g, c) is feature
+            // 16 (k >> 2) + 4g + (k & 3) of token 16 b + c, so each half of the lane's 8
+            // values is 4 consecutive features: one 8-B store per part and half
+            const uint4 hu = __builtin_bit_cast(uint4, xs[j].h), mu = __builtin_bit_cast(uint4, xs[j].m);
+            _Float16* row = &S.VT[0][tok][4 * g];
+            *reinterpret_cast<uint2*>(row) = uint2{hu.x, hu.y};
+            *reinterpret_cast<uint2*>(row + 16) = uint2{hu.z, hu.w};
+            _Float16* rowm = &S.VT[1][tok][4 * g];
+            *reinterpret_cast<uint2*>(rowm) = uint2{mu.x, mu.y};
+            *reinterpret_cast<uint2*>(rowm + 16) = uint2{mu.z, mu.w};
         }
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
@@ -567,18 +566,18 @@ __device__ inline void kv_store(KV& S, const int (&qb)[2], const float (&xn)[2][
         }
     }
 }
-template <int NB, int J0 = 0, class KV>
+template <int NB, class KV>
 __device__ inline void kv_from_y(KV& S, const int (&qb)[2], const float (&xn)[2][8], const ModelView& M) {
     Split2 xs[2];
     if constexpr (KV::kSplitK) {
 #pragma unroll
-        for (int j = J0; j < J0 + NB; ++j) xs[j] = split2(xn[j], 1.0f);  // xn = ln_1 output x 2^attn_ey (PL)
+        for (int j = 0; j < NB; ++j) xs[j] = split2(xn[j], 1.0f);  // xn = ln_1 output x 2^attn_ey (PL)
     }
-    kv_store<NB, J0>(S, qb, xn, xs);
+    kv_store<NB>(S, qb, xn, xs);
 }
 // both of the above from one split of xn (the u projection's B operand and the keys / values
 // are the same LayerNorm output at the same scale)
-template <int NB, int J0 = 0, class KV>
+template <int NB, class KV>
 __device__ inline void u_proj_kv3_n(const float* W, const FragSrc3& f3, const float (&xn)[2][8], float (&q)[2][8],
                                     KV& S, const int (&qb)[2], const ModelView& M) {
     // the G tiles first: their L2 latency runs under the split and the K/V stores
@@ -586,9 +585,9 @@ __device__ inline void u_proj_kv3_n(const float* W, const FragSrc3& f3, const fl
     ld_g(f3, wg);
     Split2 xs[2];
 #pragma unroll
-    for (int j = J0; j < J0 + NB; ++j) xs[j] = split2(xn[j], 1.0f);  // xn = ln_1 output x 2^attn_ey (PL)
-    kv_store<NB, J0>(S, qb, xn, xs);
-    u_proj3_w<NB, J0>(W, wg, xs, q, M);
+    for (int j = 0; j < NB; ++j) xs[j] = split2(xn[j], 1.0f);  // xn = ln_1 output x 2^attn_ey (PL)
+    kv_store<NB>(S, qb, xn, xs);
+    u_proj3_w<NB>(W, wg, xs, q, M);
 }
 
 // Causal flash attention of query block qb over keys [key_lo, 16*qb + c] (key_lo <= 16):
@@ -829,13 +828,9 @@ __device__ inline void load_layer_params(float* P, const ModelView& M, int tid, 
     do {                          \
         if ((nb) == 2) {          \
             constexpr int NB = 2; \
-            constexpr int J0 = 0; \
-            (void)J0;             \
             __VA_ARGS__;          \
         } else if ((nb) == 1) {   \
             constexpr int NB = 1; \
-            constexpr int J0 = 0; \
-            (void)J0;             \
             __VA_ARGS__;          \
         }                         \
     } while (0)

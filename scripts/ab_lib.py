@@ -1,4 +1,4 @@
-"""A/B of library builds (Makefile `variants`): one bandit rollout timing per library,
+"""A/B of library builds (Makefile `variant`): one bandit rollout timing per library,
 each in its own process (python scripts/ab_lib.py libA.so libB.so ...; rounds alternate).
 An argument libX.so:<bytes> runs libX.so with dpt_hip.set_cache_budget(<bytes>); a suffix +b0 / +nob0
 runs it with dpt_hip.set_block0_mfma(True / False); +nows / +nomemo run DarkRoom without the
