@@ -13,7 +13,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DPT_HIP_LIB: another build's file name in this directory (A/B runs of kernel variants)
 LIB_PATH = os.path.join(_HERE, os.environ.get("DPT_HIP_LIB", "libdpt_hip.so"))
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 DPT_OK = 0
 DPT_EINVAL = -1
@@ -202,3 +202,31 @@ SIGNATURES["dpt_rollout_bandit_generic_workspace_numel"] = (_i32, [ctypes.POINTE
                                                                    ctypes.POINTER(_i64)])
 SIGNATURES["dpt_rollout_bandit_generic"] = (_i32, [ctypes.POINTER(TrainDesc), _c_void_p,
                                                    ctypes.POINTER(BanditRolloutArgs), _c_void_p])
+
+
+class TrainData(ctypes.Structure):
+    """dpt_train_data: the fp32 training set on the device (dataset.py's ``Dataset.dataset``)."""
+    _fields_ = [("n", _i64), ("horizon", _i32), ("reserved", _i32), ("query_states", _c_void_p),
+                ("context_states", _c_void_p), ("context_actions", _c_void_p), ("context_next_states", _c_void_p),
+                ("context_rewards", _c_void_p), ("optimal_actions", _c_void_p)]
+
+
+class AdamWArgs(ctypes.Structure):
+    _fields_ = [("lr", _f64), ("beta1", _f64), ("beta2", _f64), ("eps", _f64), ("weight_decay", _f64),
+                ("step", _i64)]
+
+
+_train_desc_p = ctypes.POINTER(TrainDesc)
+_train_data_p = ctypes.POINTER(TrainData)
+SIGNATURES["dpt_train_pack_batch"] = (_i32, [_train_desc_p, _train_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                             _c_void_p, _c_void_p])
+SIGNATURES["dpt_train_ce_loss"] = (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
+                                          _c_void_p])
+SIGNATURES["dpt_adamw_step"] = (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, ctypes.POINTER(AdamWArgs),
+                                       _c_void_p])
+SIGNATURES["dpt_train_step_workspace_numel"] = (_i32, [_train_desc_p, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_train_step"] = (_i32, [_train_desc_p, _train_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                       _c_void_p, _c_void_p, ctypes.POINTER(AdamWArgs), _c_void_p, _c_void_p,
+                                       _c_void_p])
+SIGNATURES["dpt_train_eval_loss"] = (_i32, [_train_desc_p, _train_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                            _c_void_p, _c_void_p, _c_void_p])

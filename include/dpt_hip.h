@@ -1,6 +1,6 @@
 /*
  * dpt_hip.h — C ABI of libdpt_hip.so, the MI355X (gfx950) implementation of the
- * DPT data-generation + in-context-evaluation hot path.
+ * DPT data-generation, training-step and in-context-evaluation hot paths.
  *
  * Reference: titanium-47/decision-pretrained-transformer (pure Python).  The
  * reference has no FFI; its "plugin API" is three duck-typed Python protocols
@@ -37,7 +37,9 @@ extern "C" {
 
 /* 7 (round 6): dpt_policy_workspace_numel returns 0 and dpt_policy_rollout_args.workspace may be
  * NULL (each task's context lives in LDS); DPT_TUNE_POLICY_WAVE accepts only 1 */
-#define DPT_ABI_VERSION 7
+/* 8: the training step (dpt_train_pack_batch, dpt_train_ce_loss, dpt_adamw_step, dpt_train_step,
+ * dpt_train_eval_loss) */
+#define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
 #define DPT_OK 0
@@ -441,6 +443,73 @@ int dpt_rollout_bandit_generic_workspace_numel(const dpt_train_desc* desc_host, 
                                                int64_t* numel_out_host);
 int dpt_rollout_bandit_generic(const dpt_train_desc* desc_host, const float* blob,
                                const dpt_bandit_rollout_args* args_host, void* stream);
+
+/* ------------------------------------------------------------------ training step
+ * One step of train.py:286-310 (and one batch of its test loss, :265-278) as a chain of launches
+ * on one stream with no host synchronisation: pack the batch from a device-resident dataset, the
+ * training forward, CrossEntropyLoss(reduction='sum') over positions 1..T-1 and its gradient, the
+ * backward, and AdamW over the whole packed blob.  Host-side checks (null pointers, step < 1,
+ * numel < 0, action_dim > 32 -> DPT_EUNSUPPORTED, desc.window != 1 + horizon) fail before any
+ * launch.  The library allocates nothing: the weights, the optimizer state, the workspace and the
+ * loss accumulator are the caller's.                                                        */
+
+/* The whole training set on the device in fp32 (dataset.py:54-61, `Dataset.dataset`). */
+typedef struct dpt_train_data {
+    int64_t n;                        /* samples */
+    int32_t horizon;                  /* context transitions per sample */
+    int32_t reserved;                 /* 0 */
+    const float* query_states;        /* (n, sd) */
+    const float* context_states;      /* (n, horizon, sd) */
+    const float* context_actions;     /* (n, horizon, A) */
+    const float* context_next_states; /* (n, horizon, sd) */
+    const float* context_rewards;     /* (n, horizon) */
+    const float* optimal_actions;     /* (n, A) */
+} dpt_train_data;
+
+/* torch.optim.AdamW's documented update with the state of step `step` (the first step is 1):
+ *   p *= 1 - lr weight_decay;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * An entry whose gradient is exactly zero (and whose state is zero: the wpe rows past the window)
+ * only decays.  Evaluated in fp64 from the fp32 inputs, stored rounded to fp32. */
+typedef struct dpt_adamw_args {
+    double lr, beta1, beta2, eps, weight_decay;
+    int64_t step;
+} dpt_adamw_args;
+
+/* tokens (batch, 1 + horizon, 2 sd + A + 1) = the packed sequences of models/net.py:42-54 for the
+ * samples index[b] (int64, any order, repeats allowed), context transition j of sequence b taken
+ * from perm[b][j] when perm (batch, horizon) int64 is given (dataset.py:84-89), and targets
+ * (batch, A) = optimal_actions[index].  Copies only: bit-exact.  desc: state_dim, action_dim and
+ * window (= 1 + data->horizon) are read.  An index outside [0, n) or a perm entry outside
+ * [0, horizon) reads nothing and packs zeros. */
+int dpt_train_pack_batch(const dpt_train_desc* desc_host, const dpt_train_data* data_host, const int64_t* index,
+                         const int64_t* perm, int32_t batch, float* tokens, float* targets, void* stream);
+/* train.py:295-301: *loss_acc += sum over b and positions t in 1..window-1 of
+ * -sum_k targets[b][k] log_softmax(preds[b][t])[k] (probability targets, not only one-hot), and
+ * dpreds (batch, window, A) = softmax(preds) sum_k targets[b][k] - targets[b], zero at position 0
+ * (dpreds NULL: the loss alone).  A <= 32.  partial: `batch` doubles of scratch (the per-sequence
+ * losses); the sum runs in a fixed order, so repeated calls are bit-identical. */
+int dpt_train_ce_loss(const float* preds, const float* targets, int32_t batch, int32_t window, int32_t A,
+                      float* dpreds, double* partial, double* loss_acc, void* stream);
+/* one launch over blob / dblob / m / v of `numel` floats each (any numel) */
+int dpt_adamw_step(float* blob, const float* dblob, float* m, float* v, int64_t numel,
+                   const dpt_adamw_args* args_host, void* stream);
+/* workspace floats of dpt_train_step / dpt_train_eval_loss for desc.batch sequences: the training
+ * workspace, tokens, targets, preds, dpreds, dblob and the per-sequence losses */
+int dpt_train_step_workspace_numel(const dpt_train_desc* desc_host, int64_t* numel_out_host);
+/* pack -> dpt_train_forward -> cross-entropy -> dpt_train_backward -> AdamW for the `batch` <=
+ * desc.batch samples of index (a smaller last batch reuses the workspace sized for desc.batch).
+ * desc flags 0; dropout through desc.dropout / desc.dropout_seed.  blob, m, v: dpt_train_blob_numel
+ * floats, updated in place; workspace 16-byte aligned; *loss_acc += the batch's summed loss. */
+int dpt_train_step(const dpt_train_desc* desc_host, const dpt_train_data* data_host, const int64_t* index,
+                   const int64_t* perm, int32_t batch, float* blob, float* m, float* v,
+                   const dpt_adamw_args* args_host, float* workspace, double* loss_acc, void* stream);
+/* the test loss of train.py:265-278: pack -> forward only (every position, DPT_TRAIN_FORWARD_ONLY) ->
+ * cross-entropy without a gradient.  desc.dropout stays active (the reference's test loss runs in
+ * training mode).  Same workspace as dpt_train_step. */
+int dpt_train_eval_loss(const dpt_train_desc* desc_host, const dpt_train_data* data_host, const int64_t* index,
+                        const int64_t* perm, int32_t batch, const float* blob, float* workspace,
+                        double* loss_acc, void* stream);
 
 #ifdef __cplusplus
 }
