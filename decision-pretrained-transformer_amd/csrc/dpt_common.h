@@ -315,6 +315,7 @@ struct TrDims {
     uint32_t drop_thr;
     float drop_scale;
     uint64_t drop_seed;
+    int last_loss = 0;  // DPT_TRAIN_LAST_LOSS: the loss reads the last position only (no dropout, not forward-only)
     __host__ __device__ bool drop() const { return drop_thr != 0; }
     __host__ __device__ int R() const { return B * T; }
     __host__ __device__ int64_t layer_size() const { return 12ll * E * E + 13ll * E; }

@@ -449,7 +449,9 @@ __global__ void tr_attn_bwd_ds(const float* __restrict__ qkv, const float* __res
         float dp = 0.f;
         for (int e = 0; e < E; ++e) dp = fmaf(go[e], v[e], dp);
         if (site >= 0) dp *= tr_keep(d, site, ((int64_t)b * T + t) * T + j);
-        dS[pr + j] = P[pr + j] * (dp - dd);
+        // query 0 has one key: P = 1 and dp = D in exact arithmetic, so dS is exactly 0 (dp - dd would
+        // leave the two sums' rounding difference, which AdamW scales up to a full step at window 1)
+        dS[pr + j] = t == 0 ? 0.f : P[pr + j] * (dp - dd);
     }
 }
 
@@ -792,7 +794,7 @@ __global__ __launch_bounds__(256) void tr_attn_bwd_dq_mfma(const float* __restri
         const floatx4 pv = row4_load(P + ((int64_t)b * T + qc) * TP, 16 * kt + 4 * g, T);  // 0 past T
         floatx4 ds;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) ds[r] = pv[r] * (dp[r] - dd);
+        for (int r = 0; r < 4; ++r) ds[r] = qn == 0 ? 0.f : pv[r] * (dp[r] - dd);  // query 0: exactly 0 (tr_attn_bwd_ds)
         if (qn < T) row4_store(dS + ((int64_t)b * T + qn) * TP, 16 * kt + 4 * g, T, ds);
 #pragma unroll
         for (int ft = 0; ft < E / 16; ++ft)
@@ -1056,7 +1058,8 @@ static void attn_bwd_fast(int E, const float* qkv, const float* P, const float* 
 
 // DPT_TRAIN_LAST_ONLY: the last block for the last position of each sequence alone.  One wave per
 // sequence: the causal row of query T-1 over all T keys (tr_attn_fwd's arithmetic for that row).
-__global__ void tr_attn_last(const float* __restrict__ qkv, TrDims d, float* __restrict__ O) {
+__global__ void tr_attn_last(const float* __restrict__ qkv, TrDims d, float* __restrict__ O,
+                             float* __restrict__ Pout) {
     extern __shared__ float sm[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.x * (blockDim.x / 64) + wave;
@@ -1085,12 +1088,72 @@ __global__ void tr_attn_last(const float* __restrict__ qkv, TrDims d, float* __r
         l += p;
     }
     const float inv = 1.0f / wave_sum(l);
+    if (Pout)  // DPT_TRAIN_LAST_LOSS: the row's probabilities [B][T] for tr_attn_last_bwd
+        for (int j = lane; j < T; j += 64) Pout[(int64_t)b * T + j] = pr[j] * inv;
     wave_lds_sync();
     for (int e = lane; e < E; e += 64) {
         float acc = 0.f;
         for (int j = 0; j < T; ++j) acc = fmaf(pr[j], base[(int64_t)j * 3 * E + 2 * E + e], acc);
         O[(int64_t)b * E + e] = acc * inv;
     }
+}
+
+// DPT_TRAIN_LAST_LOSS: the backward of tr_attn_last, one wave per sequence.  Only query T-1 has an
+// output gradient dO [B][E]: D = dO . O, dS_j = P_j (dO . v_j - D), dv_j = P_j dO,
+// dk_j = dS_j q / sqrt(E) for every key j, dq = sum_j dS_j k_j / sqrt(E) for query T-1 and exactly 0
+// for every other query.  Writes every row of dqkv (B T, 3E).  Lanes stride over the keys, then over
+// the columns of dq with the keys in order: a fixed summation order.  LDS per wave: T + 2E floats.
+__global__ void tr_attn_last_bwd(const float* __restrict__ qkv, const float* __restrict__ Prow,
+                                 const float* __restrict__ O, const float* __restrict__ dO, TrDims d,
+                                 float* __restrict__ dqkv) {
+    extern __shared__ float sm[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (blockDim.x / 64) + wave;
+    if (b >= d.B) return;
+    const int T = d.T, E = d.E;
+    float* ds = sm + (size_t)wave * (T + 2 * E);
+    float* go = ds + T;
+    float* q = go + E;
+    const float* base = qkv + (int64_t)b * T * 3 * E;
+    float* drow = dqkv + (int64_t)b * T * 3 * E;
+    float dd = 0.f;
+    for (int e = lane; e < E; e += 64) {
+        const float g = dO[(int64_t)b * E + e];
+        go[e] = g;
+        q[e] = base[(int64_t)(T - 1) * 3 * E + e];
+        dd = fmaf(g, O[(int64_t)b * E + e], dd);
+    }
+    dd = wave_sum(dd);
+    wave_lds_sync();
+    const float rs = sqrtf((float)E);
+    for (int j = lane; j < T; j += 64) {
+        const float* v = base + (int64_t)j * 3 * E + 2 * E;
+        float dp = 0.f;
+        for (int e = 0; e < E; ++e) dp = fmaf(go[e], v[e], dp);
+        const float p = Prow[(int64_t)b * T + j];
+        const float s = p * (dp - dd);
+        ds[j] = s;
+        float* out = drow + (int64_t)j * 3 * E;
+        for (int e = 0; e < E; ++e) {
+            if (j != T - 1) out[e] = 0.f;
+            out[E + e] = s * q[e] / rs;
+            out[2 * E + e] = p * go[e];
+        }
+    }
+    wave_lds_sync();
+    for (int e = lane; e < E; e += 64) {
+        float acc = 0.f;
+        for (int j = 0; j < T; ++j) acc = fmaf(ds[j], base[(int64_t)j * 3 * E + E + e], acc);
+        drow[(int64_t)(T - 1) * 3 * E + e] = acc / rs;
+    }
+}
+
+// DPT_TRAIN_LAST_LOSS takes its own path when the window has more than one token, the compact
+// [B][A] rows fit the scratch they share with [B][4E] ones (A <= 3E) and a wave's LDS row fits;
+// otherwise the full path runs (the same predicate in the forward and the backward)
+static bool last_loss_on(const TrDims& d) {
+    return d.last_loss && !d.fwd_only && !d.drop() && d.T > 1 && d.A <= 3 * d.E &&
+           sizeof(float) * (kTrThreads / 64) * ((size_t)d.T + 2 * (size_t)d.E) <= 160 * 1024;
 }
 // dst[b][c] = src[(b T + T - 1)][c] (gather), or the reverse (scatter into the sequences' last rows)
 __global__ void tr_last_rows(const float* __restrict__ src, float* __restrict__ dst, int B, int T, int C, int scatter) {
@@ -1129,6 +1192,58 @@ int train_forward(const TrDims& d, const float* blob, const float* tok, float* w
     for (int l = 0; l < d.L; ++l) {
         const TrLayer P = TrLayer::make(B.layers + l * d.layer_size(), E);
         const int64_t sl = d.fwd_only ? 0 : l;
+        if (last_loss_on(d) && l == d.L - 1) {
+            // DPT_TRAIN_LAST_LOSS: ln_1 and c_attn on every row (the block's keys and values, saved whole
+            // with y1 / st1 for the backward), then the last query alone: its probabilities [B][T] into the
+            // P slot and [B]-row o, x2, y2, st2, hpre, x_L, yf, stf into the heads of their slots
+            const float* x = ws + W.x + l * RE;
+            float* y1 = ws + W.y1 + l * RE;
+            float* qkv = ws + W.qkv + l * RE * 3;
+            const bool fast = mm_fast(E);
+            layernorm(x, blob + P.ln1_g, blob + P.ln1_b, R, E, y1, ws + W.st1 + (int64_t)l * R * 2, st);
+            if (fast)
+                mm(E, kMmQkv, y1, blob + P.attn_w, blob + P.attn_b, nullptr, nullptr, R, qkv, st);
+            else
+                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(RE * 3)), dim3(kTrThreads), 0, st, y1, blob + P.attn_w,
+                                   blob + P.attn_b, nullptr, R, E, 3 * E, 0, qkv);
+            const int Bn = d.B;
+            const int64_t BE = (int64_t)Bn * E;
+            float* ol = ws + W.o + l * RE;
+            float* x2l = ws + W.x2 + l * RE;
+            float* y2l = ws + W.y2 + l * RE;
+            float* st2l = ws + W.st2 + (int64_t)l * R * 2;
+            float* hl = ws + W.hpre + l * RE * 4;
+            float* xnl = ws + W.x + (int64_t)d.L * RE;
+            float* xl = ws + W.dx;   // [B][E] the last rows of x (backward scratch, free in the forward)
+            float* pl = ws + W.dh;   // [B][A]
+            const size_t lds = sizeof(float) * rows_per_block * (size_t)(d.T + E);
+            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(tr_attn_last, dim3((Bn + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), lds, st,
+                               qkv, d, ol, ws + W.P + l * TT);
+            hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, x, xl, Bn, d.T, E, 0);
+            if (fast) {
+                mm(E, kMmProj, ol, blob + P.proj_w, blob + P.proj_b, xl, nullptr, Bn, x2l, st);
+            } else {
+                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, ol, blob + P.proj_w,
+                                   blob + P.proj_b, xl, Bn, E, E, 0, x2l);
+            }
+            layernorm(x2l, blob + P.ln2_g, blob + P.ln2_b, Bn, E, y2l, st2l, st);
+            if (fast) {
+                mm(E, kMmFc, y2l, blob + P.fc_w, blob + P.fc_b, nullptr, nullptr, Bn, hl, st);
+                mm(E, kMmMp, hl, blob + P.mp_w, blob + P.mp_b, x2l, nullptr, Bn, xnl, st);
+            } else {
+                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE * 4)), dim3(kTrThreads), 0, st, y2l, blob + P.fc_w,
+                                   blob + P.fc_b, nullptr, Bn, E, 4 * E, 0, hl);
+                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, hl, blob + P.mp_w,
+                                   blob + P.mp_b, x2l, Bn, 4 * E, E, 1, xnl);
+            }
+            layernorm(xnl, blob + B.lnf_g, blob + B.lnf_b, Bn, E, ws + W.yf, ws + W.stf, st);
+            hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, ws + W.yf,
+                               blob + B.head_w, blob + B.head_b, nullptr, Bn, E, d.A, 0, pl);
+            hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, pl, preds, Bn,
+                               d.T, d.A, 1);
+            return launched("train forward (last-position loss)");
+        }
         if (last_only && l == d.L - 1) {
             const float* x = ws + W.x + xs(l) * RE;
             float* y1 = ws + W.y1;
@@ -1152,7 +1267,7 @@ int train_forward(const TrDims& d, const float* blob, const float* tok, float* w
             const size_t lds = sizeof(float) * rows_per_block * (size_t)(d.T + E);
             if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipLaunchKernelGGL(tr_attn_last, dim3((Bn + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), lds, st,
-                               qkv, d, ol);
+                               qkv, d, ol, (float*)nullptr);
             hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, x, xl, Bn, d.T, E, 0);
             if (mm_fast(E)) {
                 mm(E, kMmProj, ol, blob + P.proj_w, blob + P.proj_b, xl, nullptr, Bn, x2l, st);
@@ -1235,6 +1350,97 @@ int train_forward(const TrDims& d, const float* blob, const float* tok, float* w
     return launched("train forward head");
 }
 
+// DPT_TRAIN_LAST_LOSS (last_loss_on): everything above the last block's c_attn for the B last rows.
+// Compact [B]-row scratch: dx -> W.dx, dy -> W.dy, dout -> W.dout, dh -> W.dh, dx2 -> W.dh + 4BE,
+// dpreds' last rows -> W.dh + 5BE (5BE + BA <= 4RE since T >= 2 and A <= 3E).  Leaves dx (R, E) =
+// dL/dx_{L-1}, as an iteration of train_backward's loop does.
+static int train_backward_last_top(const TrDims& d, const TrBlob& B, const TrWs& W, const float* blob, float* ws,
+                                   const float* dpreds, float* dblob, hipStream_t st) {
+    const int R = d.R(), E = d.E, Bn = d.B, l = d.L - 1;
+    const int64_t RE = (int64_t)R * E, BE = (int64_t)Bn * E, TT = (int64_t)d.B * d.T * TrWs::tpad(d.T);
+    const int rows_per_block = kTrThreads / 64;
+    const unsigned row_blocks = (R + rows_per_block - 1) / rows_per_block;
+    const unsigned brow_blocks = (Bn + rows_per_block - 1) / rows_per_block;
+    const TrLayer P = TrLayer::make(B.layers + l * d.layer_size(), E);
+    const TrLayer G = P;  // same offsets in dblob
+    float* part = ws + W.part;
+    float* dx = ws + W.dx;
+    float* dy = ws + W.dy;
+    float* dout = ws + W.dout;
+    float* dh = ws + W.dh;
+    float* dx2 = ws + W.dh + 4 * BE;
+    float* dpl = ws + W.dh + 5 * BE;
+    float* dqkv = ws + W.dqkv;
+    const float* x = ws + W.x + l * RE;
+    const float* y1 = ws + W.y1 + l * RE;
+    const float* st1 = ws + W.st1 + (int64_t)l * R * 2;
+    const float* qkv = ws + W.qkv + l * RE * 3;
+    const float* Prow = ws + W.P + l * TT;
+    const float* ol = ws + W.o + l * RE;
+    const float* x2l = ws + W.x2 + l * RE;
+    const float* y2l = ws + W.y2 + l * RE;
+    const float* st2l = ws + W.st2 + (int64_t)l * R * 2;
+    const float* hl = ws + W.hpre + l * RE * 4;
+    const float* xnl = ws + W.x + (int64_t)d.L * RE;
+    const bool fast = mm_fast(E);
+    hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, dpreds, dpl, Bn, d.T,
+                       d.A, 0);
+    // head and ln_f
+    if (int rc = wgrad(ws + W.yf, dpl, Bn, E, d.A, 0, part, dblob + B.head_w, dblob + B.head_b, st)) return rc;
+    hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dpl, blob + B.head_w, Bn, E,
+                       d.A, nullptr, nullptr, dy);
+    if (int rc = ln_param_grad(xnl, ws + W.stf, dy, Bn, E, part, dblob + B.lnf_g, dblob + B.lnf_b, st)) return rc;
+    hipLaunchKernelGGL(tr_layernorm_bwd, dim3(brow_blocks), dim3(kTrThreads), 0, st, xnl, ws + W.stf, blob + B.lnf_g, dy,
+                       Bn, E, nullptr, dx);
+    // MLP and ln_2
+    if (fast) {
+        if (int rc = wgrad_fast(E, kMmMp, hl, dx, Bn, 4 * E, E, part, dblob + G.mp_w, dblob + G.mp_b, st)) return rc;
+        mm(E, kMmBdMp, dx, blob + P.mp_w, nullptr, nullptr, hl, Bn, dh, st);
+        if (int rc = wgrad_fast(E, kMmFc, y2l, dh, Bn, E, 4 * E, part, dblob + G.fc_w, dblob + G.fc_b, st)) return rc;
+        mm(E, kMmBdFc, dh, blob + P.fc_w, nullptr, nullptr, nullptr, Bn, dy, st);
+    } else {
+        if (int rc = wgrad(hl, dx, Bn, 4 * E, E, 1, part, dblob + G.mp_w, dblob + G.mp_b, st)) return rc;
+        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(BE * 4)), dim3(kTrThreads), 0, st, dx, blob + P.mp_w, Bn,
+                           4 * E, E, hl, nullptr, dh);
+        if (int rc = wgrad(y2l, dh, Bn, E, 4 * E, 0, part, dblob + G.fc_w, dblob + G.fc_b, st)) return rc;
+        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dh, blob + P.fc_w, Bn, E,
+                           4 * E, nullptr, nullptr, dy);
+    }
+    if (int rc = ln_param_grad(x2l, st2l, dy, Bn, E, part, dblob + G.ln2_g, dblob + G.ln2_b, st)) return rc;
+    hipLaunchKernelGGL(tr_layernorm_bwd, dim3(brow_blocks), dim3(kTrThreads), 0, st, x2l, st2l, blob + P.ln2_g, dy, Bn, E,
+                       dx, dx2);
+    // c_proj, then the one query row's attention
+    if (fast) {
+        if (int rc = wgrad_fast(E, kMmProj, ol, dx2, Bn, E, E, part, dblob + G.proj_w, dblob + G.proj_b, st)) return rc;
+        mm(E, kMmBdProj, dx2, blob + P.proj_w, nullptr, nullptr, nullptr, Bn, dout, st);
+    } else {
+        if (int rc = wgrad(ol, dx2, Bn, E, E, 0, part, dblob + G.proj_w, dblob + G.proj_b, st)) return rc;
+        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dx2, blob + P.proj_w, Bn, E,
+                           E, nullptr, nullptr, dout);
+    }
+    const size_t lds = sizeof(float) * rows_per_block * ((size_t)d.T + 2 * (size_t)E);
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(tr_attn_last_bwd, dim3(brow_blocks), dim3(kTrThreads), lds, st, qkv, Prow, ol, dout, d, dqkv);
+    // the residual x2 = x + ...: dL/dx2 is dx2 at the last rows and 0 elsewhere, at full width
+    float* dx2f = ws + W.dx2;
+    if (int rc = check_hip(hipMemsetAsync(dx2f, 0, sizeof(float) * RE, st), "dx2 memset")) return rc;
+    hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dx2, dx2f, Bn, d.T, E, 1);
+    // c_attn and ln_1 on every row
+    float* dyf = ws + W.dy;
+    if (fast) {
+        if (int rc = wgrad_fast(E, kMmQkv, y1, dqkv, R, E, 3 * E, part, dblob + G.attn_w, dblob + G.attn_b, st)) return rc;
+        mm(E, kMmBdQkv, dqkv, blob + P.attn_w, nullptr, nullptr, nullptr, R, dyf, st);
+    } else {
+        if (int rc = wgrad(y1, dqkv, R, E, 3 * E, 0, part, dblob + G.attn_w, dblob + G.attn_b, st)) return rc;
+        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dqkv, blob + P.attn_w, R, E,
+                           3 * E, nullptr, nullptr, dyf);
+    }
+    if (int rc = ln_param_grad(x, st1, dyf, R, E, part, dblob + G.ln1_g, dblob + G.ln1_b, st)) return rc;
+    hipLaunchKernelGGL(tr_layernorm_bwd, dim3(row_blocks), dim3(kTrThreads), 0, st, x, st1, blob + P.ln1_g, dyf, R, E,
+                       dx2f, dx);
+    return launched("train backward (last-position loss)");
+}
+
 int train_backward(const TrDims& d, const float* blob, const float* tok, float* ws, const float* dpreds,
                    float* dblob, hipStream_t st) {
     if (int rc = train_dims_check(d)) return rc;
@@ -1249,6 +1455,14 @@ int train_backward(const TrDims& d, const float* blob, const float* tok, float* 
     float* dx2 = ws + W.dx2;
     float* dy = ws + W.dy;
     if (int rc = check_hip(hipMemsetAsync(dblob, 0, sizeof(float) * B.total, st), "dblob memset")) return rc;
+    int top = d.L - 1;  // the first block of the full-width loop below
+    if (last_loss_on(d)) {
+        // DPT_TRAIN_LAST_LOSS: the head, ln_f and the last block's MLP, ln_2 and c_proj on the [B] last
+        // rows the forward saved; the attention backward of the one query row per sequence fills every
+        // row of dqkv; from c_attn down the block runs at full width and joins the loop
+        if (int rc = train_backward_last_top(d, B, W, blob, ws, dpreds, dblob, st)) return rc;
+        top = d.L - 2;
+    } else {
     // head: preds = yf head_w + head_b
     if (int rc = wgrad(ws + W.yf, dpreds, R, E, d.A, 0, part, dblob + B.head_w, dblob + B.head_b, st)) return rc;
     hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dpreds, blob + B.head_w, R, E,
@@ -1258,9 +1472,10 @@ int train_backward(const TrDims& d, const float* blob, const float* tok, float* 
         return rc;
     hipLaunchKernelGGL(tr_layernorm_bwd, dim3(row_blocks), dim3(kTrThreads), 0, st, ws + W.x + d.L * RE, ws + W.stf,
                        blob + B.lnf_g, dy, R, E, nullptr, dx);
+    }
     const size_t ds_lds = sizeof(float) * rows_per_block * (size_t)E;
     const bool drop = d.drop();
-    for (int l = d.L - 1; l >= 0; --l) {
+    for (int l = top; l >= 0; --l) {
         const TrLayer P = TrLayer::make(B.layers + l * d.layer_size(), E);
         const TrLayer G = TrLayer::make(B.layers + l * d.layer_size(), E);  // same offsets in dblob
         const float* x = ws + W.x + l * RE;
@@ -1701,11 +1916,16 @@ __global__ void gen_select_env(const float* __restrict__ lg, GenEnv g, int h, fl
     const float* l = lg + (int64_t)task * g.A;
     const int a = select_from_logits(l, g.A, g.sample, 1.0f, u);
     const double mean = g.means[(int64_t)task * g.A + a];
+    const bool bern = (g.type & ~DPT_BANDIT_F32) == DPT_BANDIT_BERNOULLI;
     double dr;
     if (g.noise) dr = g.noise[(size_t)h * g.N + task];
-    else if (g.type == DPT_BANDIT_BERNOULLI) dr = philox_uniform(g.seed, ctr, gtask, DPT_STREAM_REWARD);
+    else if (bern) dr = philox_uniform(g.seed, ctr, gtask, DPT_STREAM_REWARD);
     else dr = philox_normal(g.seed, ctr, gtask, DPT_STREAM_REWARD);
-    const double r = g.type == DPT_BANDIT_BERNOULLI ? (dr < mean ? 1.0 : 0.0) : gaussian_reward(mean, g.var, dr);
+    double r;
+    if (bern) r = dr < mean ? 1.0 : 0.0;
+    else if (g.type & DPT_BANDIT_F32)  // GPUBanditEnv's fp32 arithmetic, as bandit_step_kernel (dpt_env.hip)
+        r = (double)__fadd_rn((float)mean, __fmul_rn((float)dr, (float)g.var));
+    else r = gaussian_reward(mean, g.var, dr);
     const size_t o = (size_t)task * g.H + h;
     g.actions_out[o] = a;
     g.rewards_out[o] = r;
@@ -1725,7 +1945,8 @@ int64_t gen_rollout_workspace_numel(const TrDims& d, int N, int H) { return GenW
 int rollout_bandit_generic(const TrDims& d, const float* blob, const dpt_bandit_rollout_args& a, hipStream_t st) {
     if (int rc = train_dims_check(d)) return rc;
     if (a.A != d.A || d.F != 2 + a.A + 1 || a.H > d.npos || a.N < 1 || a.H < 1 ||
-        (a.type != DPT_BANDIT_GAUSSIAN && a.type != DPT_BANDIT_BERNOULLI) || a.kvcache == nullptr || a.means == nullptr ||
+        ((a.type & ~DPT_BANDIT_F32) != DPT_BANDIT_GAUSSIAN && (a.type & ~DPT_BANDIT_F32) != DPT_BANDIT_BERNOULLI) ||
+        a.kvcache == nullptr || a.means == nullptr ||
         a.actions_out == nullptr || a.rewards_out == nullptr || a.arm_value_out == nullptr) {
         set_error(DPT_EINVAL, "generic bandit rollout: A=%d (model %d), state_dim must be 1, H=%d (n_positions %d), type=%d",
                   a.A, d.A, a.H, d.npos, a.type);

@@ -190,6 +190,7 @@ class TrainDesc(ctypes.Structure):
 
 TRAIN_FORWARD_ONLY = 1  # dpt_train_desc.reserved flag (DPT_TRAIN_FORWARD_ONLY)
 TRAIN_LAST_ONLY = 2  # with it: preds at the last position only (DPT_TRAIN_LAST_ONLY)
+TRAIN_LAST_LOSS = 4  # training forward / backward whose loss reads the last position only (DPT_TRAIN_LAST_LOSS)
 
 
 SIGNATURES["dpt_train_blob_numel"] = (_i32, [ctypes.POINTER(TrainDesc), ctypes.POINTER(_i64)])
@@ -230,3 +231,22 @@ SIGNATURES["dpt_train_step"] = (_i32, [_train_desc_p, _train_data_p, _c_void_p, 
                                        _c_void_p])
 SIGNATURES["dpt_train_eval_loss"] = (_i32, [_train_desc_p, _train_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
                                             _c_void_p, _c_void_p, _c_void_p])
+
+
+INTERACTIVE_ACCUMULATE = 1  # dpt_interactive_args.flags: dblob += the chunk's gradient
+INTERACTIVE_FULL_WIDTH = 2  # the last block at full width (no DPT_TRAIN_LAST_LOSS); for A/B runs
+
+
+class InteractiveArgs(ctypes.Structure):
+    """dpt_interactive_args: one chunk of an interactive (on-policy) bandit training step."""
+    _fields_ = [("N", _i32), ("K", _i32), ("type", _i32), ("flags", _i32), ("first_task", _i64),
+                ("var", _f64), ("scale", _f64), ("seed", _u64), ("counter", _u64), ("means", _c_void_p),
+                ("targets", _c_void_p), ("uniforms", _c_void_p), ("noise", _c_void_p), ("actions_out", _c_void_p),
+                ("rewards_out", _c_void_p), ("workspace", _c_void_p), ("dblob", _c_void_p), ("loss_acc", _c_void_p)]
+
+
+SIGNATURES["dpt_interactive_pack"] = (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p])
+SIGNATURES["dpt_train_ce_last"] = (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32, _f64, _c_void_p, _c_void_p,
+                                          _c_void_p, _c_void_p])
+SIGNATURES["dpt_interactive_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i32, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_interactive_grad"] = (_i32, [_train_desc_p, _c_void_p, ctypes.POINTER(InteractiveArgs), _c_void_p])

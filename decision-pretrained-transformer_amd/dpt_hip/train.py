@@ -11,6 +11,10 @@ holding the forward's saved activations is a torch tensor kept on the autograd c
 ``Trainer`` is the fused training step that train.py runs (dpt_train_step: batch packing from a
 device-resident dataset, forward, summed cross-entropy, backward, AdamW on the packed blob) with
 the master weights, the optimizer state and the loss accumulator kept on the device.
+
+``InteractiveTrainer`` is the fused on-policy bandit step that train_interactive.py runs
+(dpt_interactive_grad per chunk of envs: the y-cache rollout straight from the master blob, the
+window packed from its records, forward, last-position cross-entropy, backward; then dpt_adamw_step).
 """
 import ctypes
 
@@ -94,6 +98,7 @@ def _unpack(dblob, shapes, dtypes):
 
 FORWARD_ONLY = _lib.TRAIN_FORWARD_ONLY  # inference workspace, no backward
 LAST_ONLY = _lib.TRAIN_LAST_ONLY  # with FORWARD_ONLY: preds at the last position only (test mode)
+LAST_LOSS = _lib.TRAIN_LAST_LOSS  # training forward / backward whose loss reads the last position only
 
 
 def desc(n_layer, n_embd, state_dim, action_dim, n_positions, batch, window, flags=0, dropout=0.0, seed=0):
@@ -314,15 +319,18 @@ class Trainer:
 
 
 def rollout_bandit_generic(model, means, H, var, sample=True, bandit_type=0, seed=0, first_task=0, uniforms=None,
-                           noise=None, want_logits=False, counter=0):
+                           noise=None, want_logits=False, counter=0, f32=False, blob=None):
     """The fused online bandit rollout (evals/eval_bandit.py:56-103) for a Transformer of any width
     (dpt_rollout_bandit_generic: exact K/V-cache decode, one step for all tasks at a time, the
     draws / selection / env step of DeviceModel.rollout_bandit).  Same arguments and result dict
     as DeviceModel.rollout_bandit: actions (N,H) int32, rewards (N,H) f64, arm_value (N,H) f64,
-    logits (H,N,A) f32 if requested."""
+    logits (H,N,A) f32 if requested.  ``f32``: GPUBanditEnv's fp32 reward arithmetic (DPT_BANDIT_F32);
+    ``blob``: run on this packed blob (a trainer's master weights) instead of the module's parameters."""
     dev = device()
     means_d = _dev(means, torch.float64, dev)
     N, A = means_d.shape
+    if f32:
+        bandit_type = int(bandit_type) | _lib.BANDIT_F32
     H = int(H)
     out = dict(actions=torch.empty((N, H), dtype=torch.int32, device=dev),
                rewards=torch.empty((N, H), dtype=torch.float64, device=dev),
@@ -334,7 +342,9 @@ def rollout_bandit_generic(model, means, H, var, sample=True, bandit_type=0, see
     n = ctypes.c_int64()
     _lib.call("dpt_rollout_bandit_generic_workspace_numel", ctypes.byref(d), N, H, ctypes.byref(n))
     ws = torch.empty(n.value, dtype=torch.float32, device=dev)
-    blob = pack_params(param_list(model), dev)
+    if blob is None:
+        blob = pack_params(param_list(model), dev)
+    _on_device(blob)
     u_d = None if uniforms is None else _dev(uniforms, torch.float64, dev)
     g_d = None if noise is None else _dev(noise, torch.float64, dev)
     args = _lib.BanditRolloutArgs(
@@ -345,3 +355,113 @@ def rollout_bandit_generic(model, means, H, var, sample=True, bandit_type=0, see
     _lib.call("dpt_rollout_bandit_generic", ctypes.byref(d), _p(blob), ctypes.byref(args), _stream())
     out["_keep"] = (ws, blob, means_d, u_d, g_d)
     return out
+
+
+def chunk_plan(n, chunk):
+    """[(offset, size), ...] covering ``n`` envs in chunks of ``chunk`` (0: all at once)."""
+    n, chunk = int(n), int(chunk)
+    if n < 1 or chunk < 0:
+        raise ValueError(f"chunk_plan: n={n} chunk={chunk}")
+    size = n if chunk == 0 else min(chunk, n)
+    return [(off, min(size, n - off)) for off in range(0, n, size)]
+
+
+class InteractiveTrainer:
+    """The fused interactive (on-policy) bandit step of train_interactive.py:92-143 for a
+    models.net.Transformer with state_dim 1 and no dropout.
+
+    Built like ``Trainer``: the fp32 master blob, AdamW's ``m`` and ``v``, the gradient blob, the
+    step count, the workspace and a float64 loss accumulator live on the device.  ``step`` runs one
+    dpt_interactive_grad per chunk of envs (K - 1 sampled rollout steps from the blob, the window
+    packed from the records, forward, last-position cross-entropy scaled by 1 / N, backward), the
+    chunks' gradients added in chunk order, then one dpt_adamw_step -- all on the current stream
+    with no host synchronisation; ``read_loss`` is the only call that waits for the device."""
+
+    def __init__(self, model, lr, weight_decay=1e-4, chunk=0, betas=(0.9, 0.999), eps=1e-8, full_width=False):
+        # full_width: the last block for every row instead of the last one (DPT_INTERACTIVE_FULL_WIDTH; A/B runs)
+        self.full_width = bool(full_width)
+        if model.state_dim != 1:
+            raise ValueError(f"InteractiveTrainer: state_dim={model.state_dim} (bandits have state_dim 1)")
+        if model.dropout != 0:
+            raise ValueError("InteractiveTrainer: dropout must be 0 (the cached decode has no dropout masks)")
+        if int(chunk) < 0:
+            raise ValueError(f"InteractiveTrainer: chunk={chunk}")
+        self.model, self.chunk = model, int(chunk)
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
+        dev = device()
+        self.blob = pack_params(param_list(model), dev)
+        self.m = torch.zeros_like(self.blob)
+        self.v = torch.zeros_like(self.blob)
+        self.dblob = torch.empty_like(self.blob)
+        self.steps = 0
+        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._ws = None
+        self._ws_shape = (0, 0)  # (chunk envs, K) the workspace was sized for
+
+    def _desc(self):
+        m = self.model
+        return desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, 1, 1)
+
+    def _workspace(self, d, n, K):
+        if self._ws is not None and self._ws_shape == (n, K):
+            return self._ws
+        need = ctypes.c_int64()
+        _lib.call("dpt_interactive_workspace_numel", ctypes.byref(d), n, K, ctypes.byref(need))
+        self._ws = None  # release the old one first
+        try:
+            self._ws = torch.empty(need.value, dtype=torch.float32, device=self.blob.device)
+        except torch.cuda.OutOfMemoryError as e:
+            raise MemoryError(f"InteractiveTrainer: one chunk of {n} envs at K={K} needs a workspace of "
+                              f"{4 * need.value} bytes; pass a smaller `chunk` (now {self.chunk}; 0 = all envs at "
+                              f"once)") from e
+        self._ws_shape = (n, K)
+        return self._ws
+
+    def step(self, means, K, var, bandit_type, uniforms=None, noise=None, seed=None, targets=None):
+        """One episode: ``means`` (N, A) arm means, ``K`` the window (K - 1 rolled-out steps),
+        ``bandit_type`` 'uniform' / 'bernoulli' (or a DPT_BANDIT_* code), ``targets`` (N) int64 the
+        optimal arms (default: argmax of means, GPUBanditEnv.opt_a_index).  ``uniforms`` / ``noise``
+        (K - 1, N) inject the selection uniforms / reward draws; otherwise Philox keyed by ``seed``
+        (default: dpt_hip.next_seed()) and the env's global index.  Adds the step's mean loss to the
+        accumulator and returns the recorded (actions (N, K-1) int32, rewards (N, K-1) float64)."""
+        from . import next_seed
+        dev = self.blob.device
+        K = int(K)
+        means_d = _dev(means, torch.float64, dev)
+        if means_d.dim() != 2 or means_d.shape[1] != self.model.action_dim or means_d.shape[0] < 1:
+            raise ValueError(f"means {tuple(means_d.shape)} != (N >= 1, action_dim {self.model.action_dim})")
+        N = int(means_d.shape[0])
+        code = {"uniform": _lib.BANDIT_GAUSSIAN, "bernoulli": _lib.BANDIT_BERNOULLI}.get(bandit_type, bandit_type)
+        tg = means_d.argmax(dim=1) if targets is None else _dev(targets, torch.int64, dev).reshape(-1)
+        if tg.numel() != N:
+            raise ValueError(f"targets {tg.numel()} != envs {N}")
+        draws = []
+        for name, x in (("uniforms", uniforms), ("noise", noise)):
+            x = None if x is None else _dev(x, torch.float64, dev)
+            if x is not None and tuple(x.shape) != (K - 1, N):
+                raise ValueError(f"{name} {tuple(x.shape)} != (K - 1 = {K - 1}, N = {N})")
+            draws.append(x)
+        seed = (next_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
+        actions = torch.empty((N, max(K - 1, 0)), dtype=torch.int32, device=dev)
+        rewards = torch.empty((N, max(K - 1, 0)), dtype=torch.float64, device=dev)
+        d = self._desc()
+        plan = chunk_plan(N, self.chunk)
+        ws = self._workspace(d, plan[0][1], K)
+        base_flags = _lib.INTERACTIVE_FULL_WIDTH if self.full_width else 0
+        for i, (off, n) in enumerate(plan):
+            # rows off..off+n of the (N, K-1) records are one contiguous block; the draws' columns are copied
+            u_c, g_c = (None if x is None else x[:, off:off + n].contiguous() for x in draws)
+            args = _lib.InteractiveArgs(
+                n, K, int(code), base_flags | (_lib.INTERACTIVE_ACCUMULATE if i > 0 else 0), off, float(var), 1.0 / N, seed, 0, _p(means_d[off:off + n]).value,
+                _p(tg[off:off + n]).value, None if u_c is None else _p(u_c).value,
+                None if g_c is None else _p(g_c).value, _p(actions[off:off + n]).value,
+                _p(rewards[off:off + n]).value, _p(ws).value, _p(self.dblob).value, _p(self.loss).value)
+            _lib.call("dpt_interactive_grad", ctypes.byref(d), _p(self.blob), ctypes.byref(args), _stream())
+        self.steps += 1
+        opt = _lib.AdamWArgs(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps)
+        _lib.call("dpt_adamw_step", _p(self.blob), _p(self.dblob), _p(self.m), _p(self.v), self.blob.numel(),
+                  ctypes.byref(opt), _stream())
+        return actions, rewards
+
+    read_loss = Trainer.read_loss
+    sync_to_model = Trainer.sync_to_model

@@ -1,6 +1,6 @@
 /*
  * dpt_hip.h — C ABI of libdpt_hip.so, the MI355X (gfx950) implementation of the
- * DPT data-generation, training-step and in-context-evaluation hot paths.
+ * DPT data-generation, training-step (offline and interactive) and in-context-evaluation hot paths.
  *
  * Reference: titanium-47/decision-pretrained-transformer (pure Python).  The
  * reference has no FFI; its "plugin API" is three duck-typed Python protocols
@@ -38,7 +38,9 @@ extern "C" {
 /* 7 (round 6): dpt_policy_workspace_numel returns 0 and dpt_policy_rollout_args.workspace may be
  * NULL (each task's context lives in LDS); DPT_TUNE_POLICY_WAVE accepts only 1 */
 /* 8: the training step (dpt_train_pack_batch, dpt_train_ce_loss, dpt_adamw_step, dpt_train_step,
- * dpt_train_eval_loss) */
+ * dpt_train_eval_loss); added since without a bump (additions only): the interactive training step
+ * (dpt_interactive_pack, dpt_train_ce_last, dpt_interactive_workspace_numel, dpt_interactive_grad)
+ * and DPT_BANDIT_F32 in dpt_rollout_bandit_generic */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -399,7 +401,7 @@ int dpt_regret_moments(const double* arm_value, const double* opt, int32_t N, in
 typedef struct dpt_train_desc {
     int32_t n_layer, n_embd, state_dim, action_dim, n_positions;
     int32_t batch, window;        /* sequences and tokens per sequence (1 + context length) */
-    int32_t reserved;             /* flags: DPT_TRAIN_FORWARD_ONLY [| DPT_TRAIN_LAST_ONLY] or 0 */
+    int32_t reserved;             /* flags: DPT_TRAIN_FORWARD_ONLY [| DPT_TRAIN_LAST_ONLY], DPT_TRAIN_LAST_LOSS, or 0 */
     float dropout;                /* GPT2Config embd/attn/resid_pdrop (net.py:30-32), 0 <= p < 1 */
     int32_t reserved2;            /* 0 */
     uint64_t dropout_seed;        /* Philox key of this forward's masks (a fresh one per step) */
@@ -420,6 +422,15 @@ typedef struct dpt_train_desc {
  * (models/net.py:56-58 test mode reads preds[:, -1]); the last block runs for that position alone
  * (its keys and values still cover the window) and the other rows of preds are left unwritten */
 #define DPT_TRAIN_LAST_ONLY 2
+/* a TRAINING forward (no DPT_TRAIN_FORWARD_ONLY, no dropout) whose loss reads the last position of each
+ * sequence alone (dpt_train_ce_last): the last block's c_proj, ln_2, MLP, then ln_f and the head run
+ * for `batch` rows instead of batch * window, in the forward (which saves those rows, the last block's
+ * full q/k/v and the last query's probabilities) and in the backward (one query row per sequence: dq for
+ * that row, dK / dV for every position; from c_attn down the full-width path).  Only preds[:, window-1]
+ * is written, and dpt_train_backward reads only dpreds[:, window-1]: every row it skips contributes
+ * exact zeros to the full backward, so the gradient is the same up to fp32 summation order.  Pass the
+ * same desc to the backward.  window 1 (and action_dim > 3 n_embd) runs the full path. */
+#define DPT_TRAIN_LAST_LOSS 4
 int dpt_train_blob_numel(const dpt_train_desc* desc_host, int64_t* numel_out_host);
 int dpt_train_workspace_numel(const dpt_train_desc* desc_host, int64_t* numel_out_host);
 int dpt_train_forward(const dpt_train_desc* desc_host, const float* blob, const float* tokens, float* workspace,
@@ -436,7 +447,9 @@ int dpt_train_backward(const dpt_train_desc* desc_host, const float* blob, const
  * scores the cached rows, c_proj runs on W_v W_proj), read once per step by a flash-decoding pass.
  * args->kvcache = dpt_rollout_bandit_generic_workspace_numel floats (the y cache
  * [n_layer][N][H][n_embd], the folded weights, per-step rows); the other fields as for
- * dpt_rollout_bandit.
+ * dpt_rollout_bandit.  args->type may carry DPT_BANDIT_F32: Gaussian rewards are then
+ * float(mean) + float(g) * float(var) (two fp32 roundings, stored as double), GPUBanditEnv's
+ * arithmetic as in dpt_bandit_step; Bernoulli rewards and every other output are unchanged.
  * Replaces the per-step path (Transformer.forward over the whole window every step) at widths
  * the fused kernel is not built for.                                                        */
 int dpt_rollout_bandit_generic_workspace_numel(const dpt_train_desc* desc_host, int32_t N, int32_t H,
@@ -510,6 +523,72 @@ int dpt_train_step(const dpt_train_desc* desc_host, const dpt_train_data* data_h
 int dpt_train_eval_loss(const dpt_train_desc* desc_host, const dpt_train_data* data_host, const int64_t* index,
                         const int64_t* perm, int32_t batch, const float* blob, float* workspace,
                         double* loss_acc, void* stream);
+
+/* ------------------------------------------------------------------ interactive training step
+ * One episode of train_interactive.py:92-143 (the on-policy variant: sample fresh bandits, roll the
+ * model out for K steps with sampling, one CrossEntropyLoss() on the LAST step's logits against the
+ * optimal arm, one AdamW step) without the reference's K whole-window autograd forwards: the K - 1
+ * steps whose records reach the loss run through dpt_rollout_bandit_generic (exact y-cache decode,
+ * straight from the training blob), the window is packed from the rollout's records, and one
+ * training forward / backward at window K gives the gradient.  The reference's K-th action and
+ * reward never reach the loss and are not drawn.  ABI 8, additive.                            */
+
+/* tokens (N, Hc + 1, A + 3) from rollout records actions (N, Hc) int32 / rewards (N, Hc) fp64:
+ * row 0 = [1, 0_A, 0, 0], row 1 + j = [1, onehot(a_j), 1, float(r_j)] (models/net.py:42-54 with
+ * the bandit's state 1).  Hc = 0 (the query row alone; actions / rewards may be NULL) is legal.
+ * Copies and one double-to-float conversion: bit-exact.  An action outside [0, A) packs zeros. */
+int dpt_interactive_pack(const int32_t* actions, const double* rewards, int32_t N, int32_t Hc, int32_t A,
+                         float* tokens, void* stream);
+/* CrossEntropyLoss at the last position against class indices targets (batch) int64:
+ *   *loss_acc += scale * sum_b (lse(preds[b][window-1]) - preds[b][window-1][targets[b]])
+ *   dpreds (batch, window, A) = scale * (softmax - onehot) at the last position, exactly zero at
+ *   every other one (dpreds NULL: the loss alone).
+ * scale = 1 / (envs of the whole step), so the chunks of a step add up to CrossEntropyLoss()'s mean.
+ * fp64 per element, one rounding on the store; partial: `batch` doubles of scratch; the sum runs in
+ * a fixed order, so repeated calls are bit-identical.  A <= 32.  A target outside [0, A) adds
+ * nothing to the loss or the gradient. */
+int dpt_train_ce_last(const float* preds, const int64_t* targets, int32_t batch, int32_t window, int32_t A,
+                      double scale, float* dpreds, double* partial, double* loss_acc, void* stream);
+
+/* dpt_interactive_args.flags */
+#define DPT_INTERACTIVE_ACCUMULATE 1 /* dblob += the chunk's gradient (default: dblob = it)             */
+#define DPT_INTERACTIVE_FULL_WIDTH 2 /* the last block at full width (no DPT_TRAIN_LAST_LOSS): the same
+                                      * gradient up to fp32 summation order, slower; kept for A/B runs  */
+typedef struct dpt_interactive_args {
+    int32_t N;              /* envs of this chunk                                            */
+    int32_t K;              /* window: K - 1 rolled-out steps, then the query of step K - 1  */
+    int32_t type;           /* DPT_BANDIT_GAUSSIAN / DPT_BANDIT_BERNOULLI (DPT_BANDIT_F32 is added:
+                             * GPUBanditEnv's reward arithmetic)                             */
+    int32_t flags;          /* DPT_INTERACTIVE_* or 0                                        */
+    int64_t first_task;     /* global id of env 0 of the chunk (Philox counter)              */
+    double var;             /* reward noise std                                              */
+    double scale;           /* 1 / (envs of the whole step)                                  */
+    uint64_t seed;
+    uint64_t counter;       /* Philox counter of step 0                                      */
+    const double* means;    /* (N, A)                                                        */
+    const int64_t* targets; /* (N) optimal arm (GPUBanditEnv.opt_a_index)                    */
+    const double* uniforms; /* (K - 1, N) or NULL -> Philox, as dpt_rollout_bandit_generic   */
+    const double* noise;    /* (K - 1, N) or NULL                                            */
+    int32_t* actions_out;   /* (N, K - 1) the rollout's records, always written              */
+    double* rewards_out;    /* (N, K - 1)                                                    */
+    float* workspace;       /* dpt_interactive_workspace_numel floats, 16-byte aligned       */
+    float* dblob;           /* dpt_train_blob_numel floats                                   */
+    double* loss_acc;       /* += scale * the chunk's summed loss                            */
+} dpt_interactive_args;
+
+/* floats of workspace for a chunk of N envs at window K: the training workspace, tokens, preds,
+ * dpreds, a gradient blob, the per-env losses, and (K > 1) the rollout's workspace and arm values */
+int dpt_interactive_workspace_numel(const dpt_train_desc* desc_host, int32_t N, int32_t K, int64_t* numel_out_host);
+/* The gradient of one chunk, chained on one stream with no host synchronisation and no allocation:
+ * dpt_rollout_bandit_generic for K - 1 sampled steps from `blob` (skipped when K = 1) ->
+ * dpt_interactive_pack -> dpt_train_forward at window K (DPT_TRAIN_LAST_LOSS: the loss reads the last
+ * position only) -> dpt_train_ce_last -> dpt_train_backward (-> dblob += with
+ * DPT_INTERACTIVE_ACCUMULATE, element-wise, in a fixed order).  desc: the model's n_layer,
+ * n_embd, state_dim, action_dim, n_positions (batch / window / flags are ignored: N and K rule).
+ * Host checks fail before any launch: null pointers, N < 1, K < 1, K > n_positions, state_dim != 1,
+ * action_dim > 32 (DPT_EUNSUPPORTED), dropout != 0, a workspace that is not 16-byte aligned. */
+int dpt_interactive_grad(const dpt_train_desc* desc_host, const float* blob, const dpt_interactive_args* args_host,
+                         void* stream);
 
 #ifdef __cplusplus
 }
