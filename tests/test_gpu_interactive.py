@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+from test_gpu_train import GRAD_TOL
+
 pytestmark = pytest.mark.gpu
 
 ULP = 2.0 ** -23
@@ -263,8 +265,10 @@ def test_last_loss_gradient_vs_oracle(T, E):
     rows; one query row per sequence in the attention backward) against the float64 oracle's gradient
     of sum(preds[:, -1] * dpreds[:, -1]): 5 sequences, windows 1 (the full path), 2 and 9, width 32
     (matrix cores) and 18 (row kernels).  Its max error is within twice the error of the existing
-    full backward fed dpreds that are zero except at the last row, plus 2^-23 max|g|; the last row
-    of preds is within 1e-5 of the full forward's."""
+    full backward fed dpreds that are zero except at the last row, plus 2^-23 max|g|, and every
+    parameter's gradient is within 5 * GRAD_TOL of its largest float64 entry (test_gpu_train_grads'
+    absolute bar, which does not lean on the full backward); the last row of preds is within 1e-5
+    of the full forward's."""
     from dpt_hip import train as tr
     from oracle import dpt_oracle_torch as OT
     B, A, L = 5, 5, 2
@@ -281,6 +285,7 @@ def test_last_loss_gradient_vs_oracle(T, E):
     params = tr.param_list(m)
     g64 = [P[name_of[id(p)]].grad for p in params]
     n = len(g64)
+    ends = np.cumsum([g.numel() for g in g64])
     g64 = torch.cat([(g.t() if i in (0, n - 2) else g).reshape(-1) for i, g in enumerate(g64)]).numpy()
     m = m.cuda()
     blob = tr.pack_params(tr.param_list(m))
@@ -295,6 +300,9 @@ def test_last_loss_gradient_vs_oracle(T, E):
     err_last = np.abs(out["last"][1] - g64).max()
     print(f"last-loss T={T} E={E}: err {err_last:.3e} (full backward {err_full:.3e}), max|g| {np.abs(g64).max():.3e}")
     assert err_last <= 2 * err_full + ULP * np.abs(g64).max()
+    for p, lo, hi in zip(params, ends - [g.numel() for g in params], ends):  # the absolute bar, per parameter
+        e, scale = np.abs(out["last"][1][lo:hi] - g64[lo:hi]).max(), np.abs(g64[lo:hi]).max()
+        assert e <= 5 * GRAD_TOL * scale, (name_of[id(p)], e / scale)
     if T == 1:
         assert np.array_equal(out["last"][1], out["full"][1])
 
