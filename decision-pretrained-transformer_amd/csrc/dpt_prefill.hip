@@ -165,18 +165,30 @@ prefill_kernel(ModelView M, PrefillArgs a) {
 
 constexpr int kPrefillMaxT = 512;
 
+// The K/V buffer of the geometry that runs windows of up to t tokens (128, 256 or
+// 512: prefill_kernel<t / 32>'s static LDS).  Not proportional to t: Vt pads each
+// of its rows by 4 floats whatever the window.
+constexpr size_t prefill_kv_bytes(int t) {
+    return t == 128 ? sizeof(KVBuf<128>) : t == 256 ? sizeof(KVBuf<256>) : sizeof(KVBuf<512>);
+}
+
+// Whether a `dyn`-byte parameter block fits in LDS next to that K/V buffer: the one
+// test behind both prefill_max_window (what dpt_forward_window routes by) and the
+// launch, so a window promised to the prefill is never rejected by it.
+constexpr bool prefill_fits(size_t dyn, int t) { return dyn + prefill_kv_bytes(t) + 64 <= 160 * 1024; }
+
 // Largest window the prefill takes for this model (the parameter block must
 // fit in LDS next to the K/V buffer); 0 if none.
 int prefill_max_window(const ModelView& M) {
     const size_t dyn = sizeof(float) * (size_t)PfTop::make(M.n_layer, M.F, M.A).total;
     for (int t = kPrefillMaxT; t >= 128; t /= 2)
-        if (dyn + sizeof(KVBuf<512>) * t / 512 + 64 <= 160 * 1024) return t;
+        if (prefill_fits(dyn, t)) return t;
     return 0;
 }
 
 template <int NW>
 static int launch_nw(const ModelView& M, const PrefillArgs& a, size_t dyn, hipStream_t st) {
-    if (dyn + sizeof(KVBuf<32 * NW>) > 160 * 1024) {
+    if (!prefill_fits(dyn, 32 * NW)) {
         set_error(DPT_EUNSUPPORTED, "prefill: parameter block does not fit in LDS");
         return DPT_EUNSUPPORTED;
     }

@@ -256,6 +256,39 @@ def test_c_darkroom_oracle_equals_numpy_oracle(dim, R, horizon):
     assert np.array_equal(got["returns"], ref["returns"])
 
 
+@pytest.mark.parametrize("L,A", [(1, 1), (2, 17), (5, 2), (3, 32)])
+def test_c_bandit_oracle_equals_numpy_oracle(L, A):
+    """The float64 C bandit rollout (oracle/dpt_oracle.c, the checker of the GPU model-shape sweep)
+    is pinned to the reference's recordings only at n_layer = 4 with 5 and 20 arms.  Here it is held
+    to the plain numpy float64 restatement (oracle/dpt_oracle.py bandit_online_rollout) at other
+    layer and arm counts, one arm and the widest head included, on seeded synthetic weights: logits
+    within 1e-6 (float32-rounded float64 logits), the same actions, rewards and arm values, in its
+    K/V-cache and its re-forward form."""
+    import bench
+    from oracle import c_oracle
+    import dpt_hip
+    N, H, var = 6, 12, 0.3
+    sd, _ = bench.synthetic_state_dict(L, 1, A, H)
+    W = O.split_weights({k: v.numpy() for k, v in sd.items()}, L)
+    blob = dpt_hip.pack_weights(sd, L).numpy()
+    rs = np.random.RandomState(100 * L + A)
+    means = rs.uniform(0, 1, (N, A))
+    u, g = rs.uniform(size=(H, N)), rs.normal(size=(H, N))
+    ref = O.bandit_online_rollout(W, means, H, var, u, g, True)
+    for rec in (False, True):
+        got = c_oracle.bandit_rollout_f64(blob, L, A, 4 * (1 + H), means, H, var, u, g, True, rec, 2,
+                                          want_logits=True)
+        assert np.abs(got["logits"] - ref["logits"]).max() <= 1e-6
+        assert np.array_equal(got["actions"], ref["actions"])
+        assert np.array_equal(got["rewards"], ref["rewards"])
+        assert np.array_equal(got["cum_means"], ref["cum_means"])
+        if A > 1:
+            margin = O.boundary_margin(O.softmax_f32(ref["logits"]), u)
+            np.testing.assert_allclose(got["margin"], margin, rtol=0, atol=1e-6)
+        else:
+            assert np.isinf(got["margin"]).all()  # one arm: no interior cdf edge
+
+
 def _bandit_cases():
     """(fixture, weights, means, H, var, u, g, sample, ref actions, ref cum_means, ref rewards, ref logits)
     of every recorded reference bandit rollout (evals/eval_bandit.py:56-103 with the DPT controller)."""
