@@ -77,7 +77,8 @@ int64_t train_workspace_numel(const TrDims&);
 int64_t train_blob_numel(const TrDims&);
 int train_dims_check(const TrDims&);
 int64_t gen_rollout_workspace_numel(const TrDims&, int, int);
-int rollout_bandit_generic(const TrDims&, const float*, const dpt_bandit_rollout_args&, hipStream_t);
+int rollout_bandit_generic(const TrDims&, const float*, const dpt_bandit_rollout_args&, hipStream_t,
+                           const GenEnvAct* env = nullptr);
 
 }  // namespace dpt
 
@@ -586,6 +587,19 @@ int dpt_rollout_bandit_generic(const dpt_train_desc* d, const float* blob, const
     REQUIRE(!t.drop(), "generic bandit rollout: dropout must be 0 (an eval-mode forward)");
     if (a->N == 0 || a->H == 0) return DPT_OK;
     return rollout_bandit_generic(t, blob, *a, S(stream));
+}
+
+int dpt_rollout_bandit_generic_env(const dpt_train_desc* d, const float* blob, const dpt_bandit_rollout_args* a,
+                                   const int32_t* env_actions, int32_t random_env, int32_t* env_actions_out,
+                                   void* stream) {
+    TrDims t;
+    if (int rc = train_dims(d, t)) return rc;
+    REQUIRE(blob && a, "null pointer");
+    REQUIRE(!t.drop(), "generic bandit rollout: dropout must be 0 (an eval-mode forward)");
+    REQUIRE(random_env == 0 || random_env == 1, "generic bandit rollout: random_env=%d", random_env);
+    if (a->N == 0 || a->H == 0) return DPT_OK;
+    const GenEnvAct env{env_actions, random_env, env_actions_out};
+    return rollout_bandit_generic(t, blob, *a, S(stream), &env);
 }
 
 }  // extern "C"

@@ -321,8 +321,23 @@ struct TrDims {
     __host__ __device__ int64_t layer_size() const { return 12ll * E * E + 13ll * E; }
 };
 
+// The env action of rollout_bandit_generic when it is not the action written into the context
+// (dpt_rollout_bandit_generic_env, dpt_explore.hip): the reward and arm_value_out come from it.
+struct GenEnvAct {
+    const int32_t* env_actions;  // (H, N) injected, clamped to [0, A); or nullptr
+    int random;                  // env_actions == nullptr: 1 = min(A - 1, floor(u A)), u from DPT_STREAM_ENVACT; 0 = the selected action
+    int32_t* env_actions_out;    // (N, H) the env actions taken, or nullptr
+};
+
+// shared by the interactive and the explorer/exploiter training steps (defined in dpt_interactive.hip):
+// the shape checks of a chunk of N envs at window K >= min_K (fills `run` = the desc with batch N,
+// window K, flags 0; messages begin with `who`), and dst += src element by element in one launch
+int ia_check_shape(const dpt_train_desc* d, int32_t N, int32_t K, int32_t min_K, const char* who,
+                   dpt_train_desc& run);
+int ia_accumulate(float* dst, const float* src, int64_t numel, void* stream);
+
 struct L0Off {
-    static constexpr int G = 0;                 // Wq Wk^T: u = xn G + g0 = Wk q
+    static constexpr int G = 0;                // Wq Wk^T: u = xn G + g0 = Wk q
     static constexpr int g0 = G + kE * kE;      // Wk bq
     static constexpr int Wvp = g0 + kE;         // Wv Wproj
     static constexpr int bvp = Wvp + kE * kE;   // bv Wproj + bproj

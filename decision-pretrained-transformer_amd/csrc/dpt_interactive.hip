@@ -136,26 +136,35 @@ static int ia_ws(const dpt_train_desc* run, IaWs& w, int64_t* nblob_out) {
     return DPT_OK;
 }
 
-// the shape checks shared by the workspace query and the step; fills `run`
-static int ia_check_shape(const dpt_train_desc* d, int32_t N, int32_t K, dpt_train_desc& run) {
-    IA_REQUIRE(d != nullptr, "interactive: null desc");
-    IA_REQUIRE(N >= 1, "interactive: N=%d", N);
-    IA_REQUIRE(K >= 1, "interactive: K=%d", K);
-    IA_REQUIRE(K <= d->n_positions, "interactive: K=%d exceeds n_positions=%d", K, d->n_positions);
-    IA_REQUIRE((int64_t)N * K <= (1ll << 26), "interactive: N * K = %lld rows (use smaller chunks)",
-               (long long)N * K);
-    IA_REQUIRE(d->state_dim == 1, "interactive: state_dim=%d (bandits have state_dim 1)", d->state_dim);
+// the shape checks shared by the workspace queries and the steps of the interactive (`who` =
+// "interactive", min_K 1) and the explorer/exploiter (dpt_explore.hip) training steps; fills `run`
+int ia_check_shape(const dpt_train_desc* d, int32_t N, int32_t K, int32_t min_K, const char* who,
+                   dpt_train_desc& run) {
+    IA_REQUIRE(d != nullptr, "%s: null desc", who);
+    IA_REQUIRE(N >= 1, "%s: N=%d", who, N);
+    IA_REQUIRE(K >= min_K, "%s: K=%d (at least %d)", who, K, min_K);
+    IA_REQUIRE(K <= d->n_positions, "%s: K=%d exceeds n_positions=%d", who, K, d->n_positions);
+    IA_REQUIRE((int64_t)N * K <= (1ll << 26), "%s: N * K = %lld rows (use smaller chunks)", who, (long long)N * K);
+    IA_REQUIRE(d->state_dim == 1, "%s: state_dim=%d (bandits have state_dim 1)", who, d->state_dim);
     if (d->action_dim > kMaxA) {
-        set_error(DPT_EUNSUPPORTED, "interactive: action_dim=%d above %d", d->action_dim, kMaxA);
+        set_error(DPT_EUNSUPPORTED, "%s: action_dim=%d above %d", who, d->action_dim, kMaxA);
         return DPT_EUNSUPPORTED;
     }
-    IA_REQUIRE(d->dropout == 0.0f, "interactive: dropout=%g must be 0 (the cached decode has no dropout masks)",
+    IA_REQUIRE(d->dropout == 0.0f, "%s: dropout=%g must be 0 (the cached decode has no dropout masks)", who,
                (double)d->dropout);
     run = *d;
     run.batch = N;
     run.window = K;
     run.reserved = 0;
     return DPT_OK;
+}
+
+// dst += src over `numel` floats, one launch on `stream`
+int ia_accumulate(float* dst, const float* src, int64_t numel, void* stream) {
+    const int64_t blocks = (numel + kIaThreads - 1) / kIaThreads;
+    hipLaunchKernelGGL(ia_accumulate_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, ia_stream(stream), dst, src,
+                       numel);
+    return launched_ia("ia_accumulate");
 }
 
 }  // namespace dpt
@@ -197,7 +206,7 @@ int dpt_train_ce_last(const float* preds, const int64_t* targets, int32_t batch,
 int dpt_interactive_workspace_numel(const dpt_train_desc* d, int32_t N, int32_t K, int64_t* numel) {
     IA_REQUIRE(numel != nullptr, "interactive workspace: null numel");
     dpt_train_desc run;
-    if (int rc = ia_check_shape(d, N, K, run)) return rc;
+    if (int rc = ia_check_shape(d, N, K, 1, "interactive", run)) return rc;
     IaWs w;
     if (int rc = ia_ws(&run, w, nullptr)) return rc;
     *numel = w.total;
@@ -209,7 +218,7 @@ int dpt_interactive_grad(const dpt_train_desc* d, const float* blob, const dpt_i
     IA_REQUIRE(a->means && a->targets && a->workspace && a->dblob && a->loss_acc, "interactive grad: null pointer");
     IA_REQUIRE(a->K <= 1 || (a->actions_out && a->rewards_out), "interactive grad: null actions_out / rewards_out");
     dpt_train_desc run;
-    if (int rc = ia_check_shape(d, a->N, a->K, run)) return rc;
+    if (int rc = ia_check_shape(d, a->N, a->K, 1, "interactive", run)) return rc;
     const int base = a->type & ~DPT_BANDIT_F32;
     IA_REQUIRE(base == DPT_BANDIT_GAUSSIAN || base == DPT_BANDIT_BERNOULLI, "interactive grad: bandit type %d",
                a->type);
@@ -243,12 +252,7 @@ int dpt_interactive_grad(const dpt_train_desc* d, const float* blob, const dpt_i
     if (int rc = dpt_train_ce_last(preds, a->targets, N, K, A, a->scale, dpreds, partial, a->loss_acc, stream))
         return rc;
     if (int rc = dpt_train_backward(&fit, blob, tokens, ws + w.train, dpreds, grad, stream)) return rc;
-    if (accumulate) {
-        const int64_t blocks = (nblob + kIaThreads - 1) / kIaThreads;
-        hipLaunchKernelGGL(ia_accumulate_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, ia_stream(stream),
-                           a->dblob, grad, nblob);
-        return launched_ia("ia_accumulate");
-    }
+    if (accumulate) return ia_accumulate(a->dblob, grad, nblob, stream);
     return DPT_OK;
 }
 

@@ -1894,6 +1894,7 @@ struct GenEnv {
     double* rewards_out;
     double* arm_value_out;
     float* logits_out;
+    GenEnvAct env;  // all zero: the env is stepped with the selected action
 };
 
 // the token rows: the query [1_sd, 0_A, 0_sd, 0] at step 0 (eval_bandit.py: query state ones)
@@ -1915,7 +1916,12 @@ __global__ void gen_select_env(const float* __restrict__ lg, GenEnv g, int h, fl
     if (g.sample) u = g.uniforms ? g.uniforms[(size_t)h * g.N + task] : philox_uniform(g.seed, ctr, gtask, DPT_STREAM_SELECT);
     const float* l = lg + (int64_t)task * g.A;
     const int a = select_from_logits(l, g.A, g.sample, 1.0f, u);
-    const double mean = g.means[(int64_t)task * g.A + a];
+    // the arm the env is stepped with: the selected one, or a separate one (injected and clamped, or uniform
+    // over the arms from its own Philox stream); `a` still goes into the records and the next token
+    int ea = a;
+    if (g.env.env_actions) ea = min(g.A - 1, max(0, g.env.env_actions[(size_t)h * g.N + task]));
+    else if (g.env.random) ea = min(g.A - 1, (int)floor(philox_uniform(g.seed, ctr, gtask, DPT_STREAM_ENVACT) * g.A));
+    const double mean = g.means[(int64_t)task * g.A + ea];
     const bool bern = (g.type & ~DPT_BANDIT_F32) == DPT_BANDIT_BERNOULLI;
     double dr;
     if (g.noise) dr = g.noise[(size_t)h * g.N + task];
@@ -1930,6 +1936,7 @@ __global__ void gen_select_env(const float* __restrict__ lg, GenEnv g, int h, fl
     g.actions_out[o] = a;
     g.rewards_out[o] = r;
     g.arm_value_out[o] = mean;
+    if (g.env.env_actions_out) g.env.env_actions_out[o] = ea;
     if (g.logits_out)
         for (int k = 0; k < g.A; ++k) g.logits_out[((size_t)h * g.N + task) * g.A + k] = l[k];
     const int F = 2 * g.sd + g.A + 1;
@@ -1942,7 +1949,8 @@ __global__ void gen_select_env(const float* __restrict__ lg, GenEnv g, int h, fl
 
 int64_t gen_rollout_workspace_numel(const TrDims& d, int N, int H) { return GenWs::make(d, N, H).total; }
 
-int rollout_bandit_generic(const TrDims& d, const float* blob, const dpt_bandit_rollout_args& a, hipStream_t st) {
+int rollout_bandit_generic(const TrDims& d, const float* blob, const dpt_bandit_rollout_args& a, hipStream_t st,
+                           const GenEnvAct* env) {
     if (int rc = train_dims_check(d)) return rc;
     if (a.A != d.A || d.F != 2 + a.A + 1 || a.H > d.npos || a.N < 1 || a.H < 1 ||
         ((a.type & ~DPT_BANDIT_F32) != DPT_BANDIT_GAUSSIAN && (a.type & ~DPT_BANDIT_F32) != DPT_BANDIT_BERNOULLI) ||
@@ -1973,7 +1981,7 @@ int rollout_bandit_generic(const TrDims& d, const float* blob, const dpt_bandit_
     }
     if (attn_lds > 64 * 1024) (void)hipFuncSetAttribute(attn_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds);
     GenEnv g{N, H, a.A, 1, a.type, a.sample, a.first_task, a.var, a.seed, a.counter, a.means, a.uniforms, a.noise,
-             a.actions_out, a.rewards_out, a.arm_value_out, a.logits_out};
+             a.actions_out, a.rewards_out, a.arm_value_out, a.logits_out, env ? *env : GenEnvAct{nullptr, 0, nullptr}};
     const bool fast = mm_dec_fast(E);  // the column-split matrix-core products (mm_dec)
     float* x = ws + W.x;
     float* x2 = ws + W.x2;

@@ -29,6 +29,7 @@ STREAM_SELECT = 0
 STREAM_REWARD = 1
 STREAM_ROLLIN = 2
 STREAM_DROPOUT = 3  # training dropout masks (dpt_train_desc)
+STREAM_ENVACT = 4  # the env action drawn apart from the context action (dpt_rollout_bandit_generic_env)
 STREAM_POLICY = 16  # + arm index (baseline-policy draws)
 
 _c_void_p = ctypes.c_void_p
@@ -250,3 +251,26 @@ SIGNATURES["dpt_train_ce_last"] = (_i32, [_c_void_p, _c_void_p, _i32, _i32, _i32
                                           _c_void_p, _c_void_p])
 SIGNATURES["dpt_interactive_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i32, ctypes.POINTER(_i64)])
 SIGNATURES["dpt_interactive_grad"] = (_i32, [_train_desc_p, _c_void_p, ctypes.POINTER(InteractiveArgs), _c_void_p])
+
+
+EXPLORE_ACCUMULATE = 1  # dpt_explore_args.flags: both dblobs += the chunk's gradients
+
+
+class ExploreArgs(ctypes.Structure):
+    """dpt_explore_args: one chunk of an explorer/exploiter bandit training step."""
+    _fields_ = [("N", _i32), ("K", _i32), ("type", _i32), ("flags", _i32), ("first_task", _i64),
+                ("var", _f64), ("beta", _f64), ("scale_exploiter", _f64), ("scale_explorer", _f64),
+                ("seed", _u64), ("counter", _u64), ("means", _c_void_p), ("targets", _c_void_p),
+                ("uniforms", _c_void_p), ("noise", _c_void_p), ("env_actions", _c_void_p),
+                ("actions_out", _c_void_p), ("env_actions_out", _c_void_p), ("rewards_out", _c_void_p),
+                ("workspace", _c_void_p), ("dblob_explorer", _c_void_p), ("dblob_exploiter", _c_void_p),
+                ("loss_explorer", _c_void_p), ("loss_exploiter", _c_void_p)]
+
+
+SIGNATURES["dpt_rollout_bandit_generic_env"] = (_i32, [_train_desc_p, _c_void_p, ctypes.POINTER(BanditRolloutArgs),
+                                                       _c_void_p, _i32, _c_void_p, _c_void_p])
+SIGNATURES["dpt_train_ce_rows"] = (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _f64,
+                                          _c_void_p, _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_explore_weights"] = (_i32, [_c_void_p, _i32, _i32, _f64, _c_void_p, _c_void_p])
+SIGNATURES["dpt_explore_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i32, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_explore_grad"] = (_i32, [_train_desc_p, _c_void_p, _c_void_p, ctypes.POINTER(ExploreArgs), _c_void_p])

@@ -15,6 +15,11 @@ the master weights, the optimizer state and the loss accumulator kept on the dev
 ``InteractiveTrainer`` is the fused on-policy bandit step that train_interactive.py runs
 (dpt_interactive_grad per chunk of envs: the y-cache rollout straight from the master blob, the
 window packed from its records, forward, last-position cross-entropy, backward; then dpt_adamw_step).
+
+``ExploreExploitTrainer`` is the fused two-model step that train_explorer_exploiter.py runs
+(dpt_explore_grad per chunk of envs: the explorer's rollout with the env stepped apart, one pack, the
+exploiter's and the explorer's forward / every-position cross-entropy / backward with the advantage
+weights in between; then dpt_adamw_step for each model).
 """
 import ctypes
 
@@ -319,13 +324,19 @@ class Trainer:
 
 
 def rollout_bandit_generic(model, means, H, var, sample=True, bandit_type=0, seed=0, first_task=0, uniforms=None,
-                           noise=None, want_logits=False, counter=0, f32=False, blob=None):
+                           noise=None, want_logits=False, counter=0, f32=False, blob=None, env_actions=None,
+                           random_env=None):
     """The fused online bandit rollout (evals/eval_bandit.py:56-103) for a Transformer of any width
     (dpt_rollout_bandit_generic: exact K/V-cache decode, one step for all tasks at a time, the
     draws / selection / env step of DeviceModel.rollout_bandit).  Same arguments and result dict
     as DeviceModel.rollout_bandit: actions (N,H) int32, rewards (N,H) f64, arm_value (N,H) f64,
     logits (H,N,A) f32 if requested.  ``f32``: GPUBanditEnv's fp32 reward arithmetic (DPT_BANDIT_F32);
-    ``blob``: run on this packed blob (a trainer's master weights) instead of the module's parameters."""
+    ``blob``: run on this packed blob (a trainer's master weights) instead of the module's parameters.
+    ``env_actions`` (H, N) int32 / ``random_env=True``: step the env with these arms (clamped to
+    [0, A)) or with uniformly random ones (Philox stream STREAM_ENVACT) instead of the selected action,
+    which still goes into ``actions`` and the context (dpt_rollout_bandit_generic_env; ``random_env=False``
+    takes that entry point with the option off); the result then also holds ``env_actions`` (N, H)
+    int32, the arms the env was stepped with."""
     dev = device()
     means_d = _dev(means, torch.float64, dev)
     N, A = means_d.shape
@@ -336,6 +347,14 @@ def rollout_bandit_generic(model, means, H, var, sample=True, bandit_type=0, see
                rewards=torch.empty((N, H), dtype=torch.float64, device=dev),
                arm_value=torch.empty((N, H), dtype=torch.float64, device=dev))
     out["logits"] = torch.empty((H, N, A), dtype=torch.float32, device=dev) if want_logits else None
+    separate = env_actions is not None or random_env is not None
+    ea_d = None
+    if separate:
+        out["env_actions"] = torch.empty((N, H), dtype=torch.int32, device=dev)
+        if env_actions is not None:
+            ea_d = _dev(env_actions, torch.int32, dev)
+            if tuple(ea_d.shape) != (H, N):
+                raise ValueError(f"env_actions {tuple(ea_d.shape)} != (H = {H}, N = {N})")
     if N == 0 or H == 0:
         return out
     d = desc(model.n_layer, model.n_embd, model.state_dim, model.action_dim, model.n_positions, 1, 1)
@@ -352,8 +371,12 @@ def rollout_bandit_generic(model, means, H, var, sample=True, bandit_type=0, see
         _p(means_d).value, None if u_d is None else _p(u_d).value, None if g_d is None else _p(g_d).value,
         _p(ws).value, _p(out["actions"]).value, _p(out["rewards"]).value, _p(out["arm_value"]).value,
         None if out["logits"] is None else _p(out["logits"]).value, int(counter) & (2 ** 64 - 1))
-    _lib.call("dpt_rollout_bandit_generic", ctypes.byref(d), _p(blob), ctypes.byref(args), _stream())
-    out["_keep"] = (ws, blob, means_d, u_d, g_d)
+    if separate:
+        _lib.call("dpt_rollout_bandit_generic_env", ctypes.byref(d), _p(blob), ctypes.byref(args), _p(ea_d),
+                  int(bool(random_env)), _p(out["env_actions"]), _stream())
+    else:
+        _lib.call("dpt_rollout_bandit_generic", ctypes.byref(d), _p(blob), ctypes.byref(args), _stream())
+    out["_keep"] = (ws, blob, means_d, u_d, g_d, ea_d)
     return out
 
 
@@ -465,3 +488,138 @@ class InteractiveTrainer:
 
     read_loss = Trainer.read_loss
     sync_to_model = Trainer.sync_to_model
+
+
+class ExploreExploitTrainer:
+    """The fused explorer/exploiter bandit step of train_explorer_exploiter.py:102-192 for two
+    models.net.Transformers of one config (state_dim 1, no dropout).
+
+    Built like ``InteractiveTrainer``, twice over: each model's fp32 master blob, AdamW ``m`` / ``v``
+    and gradient blob, one step count, ONE workspace shared by the two models and two float64 loss
+    accumulators live on the device.  ``step`` runs one dpt_explore_grad per chunk of envs (the
+    explorer's K - 1 sampled rollout steps with the env stepped by a separate arm, the window packed
+    once, the exploiter's forward / every-position cross-entropy / backward, the advantage weights
+    from its row losses, the explorer's forward / weighted cross-entropy / backward), the chunks'
+    gradients added in chunk order, then one dpt_adamw_step per model -- all on the current stream
+    with no host synchronisation; ``read_losses`` is the only call that waits for the device.  The
+    advantages use the exploiter's weights from before its update."""
+
+    def __init__(self, explorer, exploiter, lr, weight_decay=1e-4, chunk=0, betas=(0.9, 0.999), eps=1e-8):
+        if explorer is exploiter:
+            raise ValueError("ExploreExploitTrainer: the explorer and the exploiter are one module")
+        cfg = [(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions) for m in (explorer, exploiter)]
+        if cfg[0] != cfg[1]:
+            raise ValueError(f"ExploreExploitTrainer: the two models differ in shape ({cfg[0]} != {cfg[1]})")
+        for m in (explorer, exploiter):
+            if m.state_dim != 1:
+                raise ValueError(f"ExploreExploitTrainer: state_dim={m.state_dim} (bandits have state_dim 1)")
+            if m.dropout != 0:
+                raise ValueError("ExploreExploitTrainer: dropout must be 0 (the cached decode has no dropout masks)")
+        if int(chunk) < 0:
+            raise ValueError(f"ExploreExploitTrainer: chunk={chunk}")
+        self.explorer, self.exploiter, self.chunk = explorer, exploiter, int(chunk)
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
+        dev = device()
+        # per model: [blob, m, v, dblob]
+        self.explorer_blob, self.exploiter_blob = (pack_params(param_list(m), dev) for m in (explorer, exploiter))
+        self._state = {}
+        for name, blob in (("explorer", self.explorer_blob), ("exploiter", self.exploiter_blob)):
+            self._state[name] = (blob, torch.zeros_like(blob), torch.zeros_like(blob), torch.empty_like(blob))
+        self.explorer_dblob, self.exploiter_dblob = self._state["explorer"][3], self._state["exploiter"][3]
+        self.steps = 0
+        self.loss_explorer = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.loss_exploiter = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._ws = None
+        self._ws_shape = (0, 0)  # (chunk envs, K) the workspace was sized for
+
+    def _desc(self):
+        m = self.explorer
+        return desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, 1, 1)
+
+    def _workspace(self, d, n, K):
+        if self._ws is not None and self._ws_shape == (n, K):
+            return self._ws
+        need = ctypes.c_int64()
+        _lib.call("dpt_explore_workspace_numel", ctypes.byref(d), n, K, ctypes.byref(need))
+        self._ws = None  # release the old one first
+        try:
+            self._ws = torch.empty(need.value, dtype=torch.float32, device=self.explorer_blob.device)
+        except torch.cuda.OutOfMemoryError as e:
+            raise MemoryError(f"ExploreExploitTrainer: one chunk of {n} envs at K={K} needs a workspace of "
+                              f"{4 * need.value} bytes; pass a smaller `chunk` (now {self.chunk}; 0 = all envs at "
+                              f"once)") from e
+        self._ws_shape = (n, K)
+        return self._ws
+
+    def step(self, means, K, var, bandit_type, beta, uniforms=None, noise=None, env_actions=None, seed=None,
+             targets=None):
+        """One episode: ``means`` (N, A) arm means, ``K`` >= 2 the window (K - 1 rolled-out steps),
+        ``bandit_type`` 'uniform' / 'bernoulli' (or a DPT_BANDIT_* code), ``beta`` the advantage
+        temperature, ``targets`` (N) int64 the optimal arms (default: argmax of means).  ``uniforms`` /
+        ``noise`` (K - 1, N) inject the explorer's selection uniforms / the reward draws and
+        ``env_actions`` (K - 1, N) int32 the arms the env is stepped with; otherwise Philox keyed by
+        ``seed`` (default: dpt_hip.next_seed()) and the env's global index.  Adds the step's two mean
+        losses to the accumulators and returns the records (context actions (N, K-1) int32, env
+        actions (N, K-1) int32, rewards (N, K-1) float64)."""
+        from . import next_seed
+        dev = self.explorer_blob.device
+        K, beta = int(K), float(beta)
+        A = self.explorer.action_dim
+        if K < 2:
+            raise ValueError(f"ExploreExploitTrainer: K={K} (the explorer's loss is a mean over K - 1 positions: "
+                             f"K >= 2)")
+        means_d = _dev(means, torch.float64, dev)
+        if means_d.dim() != 2 or means_d.shape[1] != A or means_d.shape[0] < 1:
+            raise ValueError(f"means {tuple(means_d.shape)} != (N >= 1, action_dim {A})")
+        N = int(means_d.shape[0])
+        code = {"uniform": _lib.BANDIT_GAUSSIAN, "bernoulli": _lib.BANDIT_BERNOULLI}.get(bandit_type, bandit_type)
+        tg = means_d.argmax(dim=1) if targets is None else _dev(targets, torch.int64, dev).reshape(-1)
+        if tg.numel() != N:
+            raise ValueError(f"targets {tg.numel()} != envs {N}")
+        draws = []
+        for name, x, dt in (("uniforms", uniforms, torch.float64), ("noise", noise, torch.float64),
+                            ("env_actions", env_actions, torch.int32)):
+            x = None if x is None else _dev(x, dt, dev)
+            if x is not None and tuple(x.shape) != (K - 1, N):
+                raise ValueError(f"{name} {tuple(x.shape)} != (K - 1 = {K - 1}, N = {N})")
+            draws.append(x)
+        seed = (next_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
+        actions = torch.empty((N, K - 1), dtype=torch.int32, device=dev)
+        env_acts = torch.empty((N, K - 1), dtype=torch.int32, device=dev)
+        rewards = torch.empty((N, K - 1), dtype=torch.float64, device=dev)
+        d = self._desc()
+        plan = chunk_plan(N, self.chunk)
+        ws = self._workspace(d, plan[0][1], K)
+        for i, (off, n) in enumerate(plan):
+            # rows off..off+n of the (N, K-1) records are one contiguous block; the draws' columns are copied
+            u_c, g_c, e_c = (None if x is None else x[:, off:off + n].contiguous() for x in draws)
+            args = _lib.ExploreArgs(
+                n, K, int(code), _lib.EXPLORE_ACCUMULATE if i > 0 else 0, off, float(var), beta, 1.0 / (N * K),
+                1.0 / (N * (K - 1)), seed, 0, _p(means_d[off:off + n]).value, _p(tg[off:off + n]).value,
+                *(None if x is None else _p(x).value for x in (u_c, g_c, e_c)), _p(actions[off:off + n]).value,
+                _p(env_acts[off:off + n]).value, _p(rewards[off:off + n]).value, _p(ws).value,
+                _p(self.explorer_dblob).value, _p(self.exploiter_dblob).value, _p(self.loss_explorer).value,
+                _p(self.loss_exploiter).value)
+            _lib.call("dpt_explore_grad", ctypes.byref(d), _p(self.explorer_blob), _p(self.exploiter_blob),
+                      ctypes.byref(args), _stream())
+        self.steps += 1
+        opt = _lib.AdamWArgs(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps)
+        for blob, m, v, dblob in (self._state["exploiter"], self._state["explorer"]):
+            _lib.call("dpt_adamw_step", _p(blob), _p(dblob), _p(m), _p(v), blob.numel(), ctypes.byref(opt), _stream())
+        return actions, env_acts, rewards
+
+    def read_losses(self):
+        """The accumulated (explorer, exploiter) loss sums (one device synchronisation), then reset."""
+        both = torch.cat([self.loss_explorer, self.loss_exploiter]).cpu()
+        self.loss_explorer.zero_()
+        self.loss_exploiter.zero_()
+        return float(both[0]), float(both[1])
+
+    def sync_to_models(self):
+        """Unpack the two master blobs into the modules' parameters (wte is untouched)."""
+        with torch.no_grad():
+            for model, blob in ((self.explorer, self.explorer_blob), (self.exploiter, self.exploiter_blob)):
+                params = param_list(model)
+                for p, w in zip(params, _unpack(blob, [p.shape for p in params], [p.dtype for p in params])):
+                    p.copy_(w)
+        return self.explorer, self.exploiter

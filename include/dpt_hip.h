@@ -1,6 +1,7 @@
 /*
  * dpt_hip.h — C ABI of libdpt_hip.so, the MI355X (gfx950) implementation of the
- * DPT data-generation, training-step (offline and interactive) and in-context-evaluation hot paths.
+ * DPT data-generation, training-step (offline, interactive and explorer/exploiter) and
+ * in-context-evaluation hot paths.
  *
  * Reference: titanium-47/decision-pretrained-transformer (pure Python).  The
  * reference has no FFI; its "plugin API" is three duck-typed Python protocols
@@ -40,7 +41,9 @@ extern "C" {
 /* 8: the training step (dpt_train_pack_batch, dpt_train_ce_loss, dpt_adamw_step, dpt_train_step,
  * dpt_train_eval_loss); added since without a bump (additions only): the interactive training step
  * (dpt_interactive_pack, dpt_train_ce_last, dpt_interactive_workspace_numel, dpt_interactive_grad)
- * and DPT_BANDIT_F32 in dpt_rollout_bandit_generic */
+ * and DPT_BANDIT_F32 in dpt_rollout_bandit_generic; the explorer/exploiter training step
+ * (dpt_rollout_bandit_generic_env, DPT_STREAM_ENVACT, dpt_train_ce_rows, dpt_explore_weights,
+ * dpt_explore_workspace_numel, dpt_explore_grad) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -65,7 +68,8 @@ extern "C" {
 #define DPT_STREAM_REWARD 1
 #define DPT_STREAM_ROLLIN 2
 #define DPT_STREAM_DROPOUT 3 /* training dropout masks: counter (site, element / 4), word element % 4 */
-#define DPT_STREAM_POLICY 16 /* + arm index: baseline-policy draws (Thompson posterior samples) */
+#define DPT_STREAM_ENVACT 4  /* the env action of dpt_rollout_bandit_generic_env when it is drawn apart from the context action */
+#define DPT_STREAM_POLICY 16/* + arm index: baseline-policy draws (Thompson posterior samples) */
 
 int dpt_abi_version(void);
 const char* dpt_last_error(void);
@@ -589,6 +593,92 @@ int dpt_interactive_workspace_numel(const dpt_train_desc* desc_host, int32_t N, 
  * action_dim > 32 (DPT_EUNSUPPORTED), dropout != 0, a workspace that is not 16-byte aligned. */
 int dpt_interactive_grad(const dpt_train_desc* desc_host, const float* blob, const dpt_interactive_args* args_host,
                          void* stream);
+
+/* ------------------------------------------------------------------ explorer/exploiter training step
+ * One episode of train_explorer_exploiter.py:102-192 for two models of one config.  The explorer's
+ * sampled action goes into the context while the env is stepped with a uniformly random arm; the
+ * exploiter's per-step loss l_t = CE(last-position logits, optimal arm) gives the advantages
+ * adv[:, t-1] = l_t - l_{t-1}; the exploiter takes the mean CE over all N K positions of the final
+ * K-token window, the explorer the mean over N (K-1) of exp(adv / beta) CE(logits_j, context action j).
+ * Nothing the exploiter produces reaches the context, attention is causal and the query token sits at
+ * position 0, so its step-t logits are row t of ONE forward over the final window -- the forward its
+ * update needs anyway -- and only the explorer is decoded step by step (K - 1 steps of the y-cache
+ * rollout; the K-th action and reward reach neither loss and are not drawn).  ABI 8, additive.   */
+
+/* dpt_rollout_bandit_generic with the env action apart from the context action: the selected action
+ * still goes to actions_out and into the next token, while the reward and arm_value_out come from
+ *   env_actions (H, N) int32 (laid out like uniforms) when given -- device memory, so a value outside
+ *     [0, A) cannot be rejected on the host and is CLAMPED into [0, A) -- or
+ *   min(A - 1, floor(u A)), u = Philox(seed, (counter + h, first_task + i, DPT_STREAM_ENVACT)) when
+ *     env_actions is NULL and random_env = 1.
+ * env_actions NULL and random_env 0: the selected action, every output bit-identical to
+ * dpt_rollout_bandit_generic.  env_actions_out (N, H) or NULL: the env actions taken.            */
+int dpt_rollout_bandit_generic_env(const dpt_train_desc* desc_host, const float* blob,
+                                   const dpt_bandit_rollout_args* args_host, const int32_t* env_actions,
+                                   int32_t random_env, int32_t* env_actions_out, void* stream);
+
+/* Cross-entropy with class targets at EVERY position of preds (batch, window, A).  Exactly one of
+ * targets_seq (batch) int64 (one class per sequence, broadcast over its positions) and targets_row
+ * (batch, window) int32 is non-NULL; weights (batch, window) double or NULL (all ones).
+ *   rowloss (batch, window) double = lse(x) - x[target], unweighted
+ *   dpreds = scale * w * (softmax - onehot), exactly 0 where w == 0 (dpreds NULL: no gradient)
+ *   *loss_acc += scale * sum_rows w * rowloss
+ * fp64 per element from the fp32 logits, one rounding on the store; the sum runs in a fixed order
+ * (rows thread-strided in index order, then an LDS tree), so repeated calls are bit-identical.
+ * A <= 32.  A target outside [0, A): zero rowloss, zero loss, zero gradient for that row.          */
+int dpt_train_ce_rows(const float* preds, const int64_t* targets_seq, const int32_t* targets_row,
+                      const double* weights, int32_t batch, int32_t window, int32_t A, double scale,
+                      double* rowloss, float* dpreds, double* loss_acc, void* stream);
+/* The explorer's advantage weights from the exploiter's row losses, in double:
+ *   w[b][j] = exp((rowloss[b][j+1] - rowloss[b][j]) * inv_beta) for j < window - 1, w[b][window-1] = 0 */
+int dpt_explore_weights(const double* rowloss, int32_t batch, int32_t window, double inv_beta, double* weights,
+                        void* stream);
+
+#define DPT_EXPLORE_ACCUMULATE 1 /* both dblobs += the chunk's gradients (default: = them) */
+typedef struct dpt_explore_args {
+    int32_t N;                 /* envs of this chunk                                              */
+    int32_t K;                 /* window >= 2: K - 1 rolled-out steps                             */
+    int32_t type;              /* DPT_BANDIT_GAUSSIAN / DPT_BANDIT_BERNOULLI (DPT_BANDIT_F32 is added) */
+    int32_t flags;             /* DPT_EXPLORE_ACCUMULATE or 0                                     */
+    int64_t first_task;        /* global id of env 0 of the chunk (Philox counter)                */
+    double var;                /* reward noise std                                                */
+    double beta;               /* advantage temperature, finite and > 0                           */
+    double scale_exploiter;    /* 1 / (envs of the whole step * K)                                */
+    double scale_explorer;     /* 1 / (envs of the whole step * (K - 1))                          */
+    uint64_t seed;
+    uint64_t counter;          /* Philox counter of step 0                                        */
+    const double* means;       /* (N, A)                                                          */
+    const int64_t* targets;    /* (N) optimal arm (GPUBanditEnv.opt_a_index)                      */
+    const double* uniforms;    /* (K - 1, N) the explorer's selection uniforms, or NULL -> Philox */
+    const double* noise;       /* (K - 1, N) or NULL                                              */
+    const int32_t* env_actions; /* (K - 1, N) the arms the env is stepped with (clamped to [0, A)), or
+                                 * NULL -> uniform over the arms from DPT_STREAM_ENVACT            */
+    int32_t* actions_out;      /* (N, K - 1) the context actions (the explorer's), always written */
+    int32_t* env_actions_out;  /* (N, K - 1) the env actions taken, always written                */
+    double* rewards_out;       /* (N, K - 1)                                                      */
+    float* workspace;          /* dpt_explore_workspace_numel floats, 16-byte aligned             */
+    float* dblob_explorer;     /* dpt_train_blob_numel floats each, distinct                      */
+    float* dblob_exploiter;
+    double* loss_explorer;     /* += scale_explorer * sum w CE(explorer rows, context actions)    */
+    double* loss_exploiter;    /* += scale_exploiter * sum CE(exploiter rows, targets)            */
+} dpt_explore_args;
+
+/* floats of workspace for a chunk of N envs at window K: ONE training workspace, token buffer and
+ * preds / dpreds pair shared by the two models (the exploiter's pass ends on the stream before the
+ * explorer's begins), a gradient blob, and on top of that the row losses, the weights, the row
+ * targets, the rollout's workspace and its arm values */
+int dpt_explore_workspace_numel(const dpt_train_desc* desc_host, int32_t N, int32_t K, int64_t* numel_out_host);
+/* The gradients of one chunk for both models, one chain of launches on one stream with no host
+ * synchronisation and no allocation: the explorer's rollout for K - 1 sampled steps (env stepped
+ * apart) -> dpt_interactive_pack -> exploiter dpt_train_forward (full width) -> dpt_train_ce_rows
+ * against targets -> exploiter dpt_train_backward -> dpt_explore_weights -> explorer forward ->
+ * dpt_train_ce_rows with the weights against the recorded context actions (position K - 1 has
+ * weight 0) -> explorer backward.  The advantages use exploiter_blob as passed (apply AdamW to
+ * both models after the last chunk: dpt_adamw_step).  Host checks fail before any launch:
+ * everything dpt_interactive_grad checks, K < 2, beta not finite or <= 0, null or equal blobs,
+ * null or equal gradient blobs. */
+int dpt_explore_grad(const dpt_train_desc* desc_host, const float* explorer_blob, const float* exploiter_blob,
+                     const dpt_explore_args* args_host, void* stream);
 
 #ifdef __cplusplus
 }
