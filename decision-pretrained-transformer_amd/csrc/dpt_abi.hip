@@ -67,6 +67,7 @@ int set_decode_tile(int);
 int set_darkroom_memo(int);
 int set_cache_budget(int64_t);
 int set_block0_mfma(int);
+int set_ycache_bits(int);
 int set_select_fast(int);
 int regret_max_steps();
 int64_t regret_workspace_numel(int N, int H);
@@ -231,6 +232,10 @@ int dpt_tuning_set(int32_t key, int64_t value) {
     if (key == DPT_TUNE_BLOCK0_MFMA) {
         REQUIRE(value == 0 || value == 1, "block-0 MFMA %lld: 0 or 1", (long long)value);
         return set_block0_mfma((int)value);
+    }
+    if (key == DPT_TUNE_YCACHE_BITS) {
+        REQUIRE(set_ycache_bits((int)value) == DPT_OK, "y cache bits %lld: 24 or 32", (long long)value);
+        return DPT_OK;
     }
     set_error(DPT_EINVAL, "unknown tuning key %d", key);
     return DPT_EINVAL;

@@ -56,7 +56,8 @@ struct ModelView {
     const float* head_w;  // [E][A]
     const float* head_b;  // [A]
     // every block's attention folded (L0Off, one block per layer): G = Wq Wk^T,
-    // g0 = Wk bq, Wvp = Wv Wproj, bvp = bv Wproj + bproj
+    // g0 = Wk bq, Wvp = Wv Wproj, bvp = bv Wproj + bproj; then a second set of n_layer blocks with
+    // ln_1's g and b folded in for blocks >= 1 (the bandit rollout's packed y cache, derive_l0_kernel)
     const float* l0;
     int n_layer, sd, A, F, n_positions;
     // MLP products on fp16 two-part splits (dpt_mfma_fwd.h Split2): c_fc / mlp.c_proj

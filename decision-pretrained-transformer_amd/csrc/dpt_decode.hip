@@ -21,7 +21,9 @@
 // attention weights (dpt_common.h L0Off): block 0 recomputes its inputs from
 // 8-B token records, blocks >= 1 cache y = LN1(h) (128 B per position) as both
 // key and value, the u = y G + g0 projection replaces c_attn, and c_proj +
-// ln_2 run per task inside the attention wave (proj_ln_task).
+// ln_2 run per task inside the attention wave (proj_ln_task).  By default the
+// cached row is the normalised (h - mean) rstd as 24-bit fixed point, 96 B per
+// position, with ln_1's g and b folded into the derived weights (dpt_ycache.h).
 // Small parameters (embedding, LayerNorm, biases, head) and the tile's bandit
 // means live in LDS for the whole launch.  Phases inside one position are
 // separated by LDS-only barriers (lgkmcnt + s_barrier: the K/V stores of the
@@ -30,6 +32,7 @@
 // tile resident for all H steps (tasks never interact, so no inter-workgroup
 // synchronisation exists anywhere).
 #include "dpt_common.h"
+#include "dpt_ycache.h"
 
 // DPT_STAMPS (diagnostic build only, libdpt_hip_stamps.so): s_memtime after
 // every barrier of decode_position, accumulated per phase by workgroup 0
@@ -80,7 +83,8 @@ __device__ inline float* tokrec(float* kv, int max_pos, int tile0, int p, int ti
 // l >= 1 keep their y rows tile-interleaved, [tile][position][task in tile][E], so
 // a tile's 8 (16) attention waves streaming the same positions read one
 // contiguous range (DRAM page locality: -1.4 % at config 2, -3.8 % on the linear
-// config against per-task streams; bit-identical).
+// config against per-task streams; bit-identical).  The packed rows (dpt_ycache.h)
+// keep the tile's tasks adjacent per 8-position group: [tile][group][task][8 rows x 96 B].
 
 struct Smem {
     float x[kM][kE];             // residual stream of the current position
@@ -257,12 +261,19 @@ __device__ inline void tail_rows(int rem, F&& f) {
 // Cached rows of positions < pin (wave-uniform, a multiple of 8 * NR) are read with
 // the default cache policy, later ones non-temporally (see BanditRolloutParams::pin).
 // Accumulators are packed pairs (lo = dims 4c, 4c+1; hi = 4c+2, 4c+3).
-template <bool KV_SAME = false, int NR = kRows, int PS = kE>
+// YQT > 0 (with KV_SAME; the rollout's packed y cache, dpt_ycache.h): kc is the start of the
+// tile's packed rows of this block, YQT the tile size, yt the task's slot in the tile and ymax
+// the horizon; the rows are yhat 2^28 once unpacked, q is g * u, kcur holds yhat 2^28 of the
+// current position, and the result is sum_p P_p yhat_p (the 2^-28 in the score scale and in the
+// final normalisation).
+template <bool KV_SAME = false, int NR = kRows, int PS = kE, int YQT = 0>
 __device__ __attribute__((always_inline)) inline float4 attend_one(const float* __restrict__ kc, const float* __restrict__ vc, int pos,
                                     const float* q, const float* kcur, const float* vcur, float* o,
-                                    int lane, int pin = 0) {
+                                    int lane, int pin = 0, int yt = 0, int ymax = 0) {
+    static_assert(YQT == 0 || KV_SAME, "the packed rows are one stream");
     const int g = lane >> 3, c = lane & 7;
-    const float scale = 0.17677669529663687f * 1.4426950408889634f;  // 32 ** -0.5 * log2(e): exp2 domain
+    // 32 ** -0.5 * log2(e): exp2 domain
+    const float scale = 0.17677669529663687f * 1.4426950408889634f * (YQT ? kYqUnscale : 1.0f);
     const floatx4 q4 = *reinterpret_cast<const floatx4*>(q + 4 * c);
     float m = -1e30f, l = 0.f;
     f2 alo = {0.f, 0.f}, ahi = {0.f, 0.f};
@@ -285,7 +296,36 @@ __device__ __attribute__((always_inline)) inline float4 attend_one(const float* 
         constexpr int R = decltype(nrc)::value;
         constexpr bool FULL = decltype(fullc)::value;
         floatx4 kk[R], vv[R];
-        if constexpr (KV_SAME && !FULL) {
+        if constexpr (YQT > 0) {
+            // packed rows: 12 B per lane (buffer_load_dwordx3), unpacked after every load has issued
+            typedef unsigned uintx3 __attribute__((ext_vector_type(3)));
+            uintx3 pk[R];
+            if constexpr (FULL) {
+                // whole chunk: 8 groups of 8 positions, each one 768-B run of this task (the lane's
+                // 12 B at lane * 12), YQT runs apart; all of them lie in whole groups (base + 8 R <= pos
+                // < ymax)
+                const int voff = yt * kYqGroupBytes + lane * 12;
+                const int sbase = __builtin_amdgcn_readfirstlane((base >> 3) * YQT * kYqGroupBytes);
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    pk[r] = __builtin_bit_cast(uintx3, __builtin_amdgcn_raw_buffer_load_b96(
+                                                           rs, voff, sbase + r * YQT * kYqGroupBytes, NT ? 2 : 0));
+            } else {
+                // the partial last chunk: rows past pos re-read position pos - 1 (masked below)
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int pm = min(base + 8 * r + g, pos - 1);
+                    pk[r] = __builtin_bit_cast(uintx3, __builtin_amdgcn_raw_buffer_load_b96(
+                                                           rs, (int)yq_row_offset(pm, yt, YQT, ymax) + 12 * c, 0, NT ? 2 : 0));
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const YqLane p = {pk[r].x, pk[r].y, pk[r].z};
+                kk[r] = floatx4{yq_unpack_f28<0>(p), yq_unpack_f28<1>(p), yq_unpack_f28<2>(p), yq_unpack_f28<3>(p)};
+                vv[r] = kk[r];
+            }
+        } else if constexpr (KV_SAME && !FULL) {
             // the partial last chunk: rows past pos re-read position pos - 1 (masked in the scores
             // below), so every load is unconditional and they issue back to back
 #pragma unroll
@@ -404,7 +444,7 @@ __device__ __attribute__((always_inline)) inline float4 attend_one(const float* 
         m = mn;
     }
     // every lane holds dims 4c..4c+3 of the result after the butterfly
-    const float inv = 1.0f / l;
+    const float inv = (YQT ? kYqUnscale : 1.0f) / l;
     alo *= splat2(inv);
     ahi *= splat2(inv);
     const float4 res = make_float4(alo.x, alo.y, ahi.x, ahi.y);
@@ -824,7 +864,11 @@ __device__ inline void zero_smem(Smem& S) {
 // the same y stream serves as keys and values.  D is the RolloutLDS block.
 // L0M (bandit rollout, tile 8): block 0's attention on the matrix cores for NA = L0M
 // token kinds (l0_tiles + l0_merge) instead of one wave per task (attend_l0).
-template <int TILE, bool L0R = false, bool GL = false, int L0M = 0>
+// YQ (bandit rollout): blocks >= 1 cache the normalised row yhat_p = (h_p - mean_p) rstd_p as
+// packed 24-bit fixed point (96 B per position, dpt_ycache.h) and run on the second set of
+// folded weights (derive_l0_kernel), which carries ln_1's g and b: y_p . u = yhat_p . (g * u) +
+// b . u (the second term shifts every score alike) and sum_p P_p y_p = g * (sum_p P_p yhat_p) + b.
+template <int TILE, bool L0R = false, bool GL = false, int L0M = 0, bool YQ = false>
 __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, const ModelView& M,
                                 float* __restrict__ kv, int N, int max_pos, int tile0, int pos, float wpe_j,
                                 const float* D = nullptr, int pin = 0, int pin_x = 0) {
@@ -870,7 +914,7 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
             if (wave < 2) {
                 // G from LDS (GL: the rollout's LDS block has room for it) or from L2
                 const float* B = GL ? D + RolloutLDS::make(M.A, M.n_layer).G + li * kE * kE + wave * 16
-                                    : M.l0 + (size_t)li * L0Off::size + L0Off::G + wave * 16;
+                                    : M.l0 + (size_t)(li + (YQ ? M.n_layer : 0)) * L0Off::size + L0Off::G + wave * 16;
                 float w[8];
 #pragma unroll
                 for (int s = 0; s < 8; ++s) w[s] = GL ? B[(4 * s + kq) * kE + i16] : __ldg(B + (4 * s + kq) * kE + i16);
@@ -955,7 +999,8 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
                 const float* kc = kv + li * lstride + (size_t)task * max_pos * kE;
                 // the rollout's y rows are tile-interleaved: one position of the tile's tasks is
                 // TILE adjacent rows
-                const float* yc = kv + li * lstride + (size_t)tile0 * max_pos * kE + wave * kE;
+                const float* yt0 = kv + li * lstride + (size_t)tile0 * max_pos * kE;  // the tile's rows
+                const float* yc = yt0 + wave * kE;
                 constexpr int YPS = TILE * kE;
                 const float* vc = kv + vhalf + li * lstride + (size_t)task * max_pos * kE;
                 if (L0R) {
@@ -968,6 +1013,8 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
                                        D + rl.base, P + pl.emb_w + (2 + M.A) * kE, PL + PLay::ln1_g,
                                        PL + PLay::ln1_b, nullptr, lane)
                            // scores y_p . u, output sum_p P_p y_p; y_pos is in S.kcur
+                        : YQ ? attend_one<true, kYRows, YPS, YQ ? TILE : 0>(yt0, yt0, pos, S.q[wave], S.kcur[wave],
+                                                                           S.kcur[wave], nullptr, lane, lpin(li), wave, max_pos)
                            : attend_one<true, kYRows, YPS>(yc, yc, pos, S.q[wave], S.kcur[wave], S.kcur[wave], nullptr,
                                                       lane, lpin(li));
                     // c_proj (folded Wvp) + residual + ln_2 of this task, in this wave
@@ -1067,9 +1114,31 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
             const bool last = li + 1 == M.n_layer;
             const float g = last ? P[pl.lnf_g + j] : PL[PLay::size + PLay::ln1_g + j];
             const float b = last ? P[pl.lnf_b + j] : PL[PLay::size + PLay::ln1_b + j];
-            const float y = ln_halfwave(x, g, b);
+            float mean, rstd;
+            const float y = ln_halfwave(x, g, b, &mean, &rstd);
             S.xn[t][j] = y;
-            if (L0R && !last) {  // block li+1's y at `pos`: its K/V-cache row (128 B per half-wave)
+            if (L0R && YQ && !last) {
+                // block li+1's yhat at `pos`: 2^28 yhat to LDS (the form the cached rows unpack to), the
+                // packed row (96 B per half-wave) to the cache.  Every lane of a quad gets the quad's
+                // four values (quad_perm broadcasts); lanes 0..2 of it store one dword each of the
+                // quad's 12 B.
+                const float yh = (x - mean) * rstd;
+                S.kcur[t][j] = yh * (kYqScale * 256.0f);
+                const int qv = yq_quant(yh);
+                const YqLane pk = yq_pack(__builtin_amdgcn_update_dpp(0, qv, 0x00, 0xF, 0xF, false),
+                                          __builtin_amdgcn_update_dpp(0, qv, 0x55, 0xF, 0xF, false),
+                                          __builtin_amdgcn_update_dpp(0, qv, 0xAA, 0xF, 0xF, false),
+                                          __builtin_amdgcn_update_dpp(0, qv, 0xFF, 0xF, 0xF, false));
+                const int k = j & 3;
+                const unsigned word = k == 0 ? pk.h01 : k == 1 ? pk.h23 : pk.lo;
+                unsigned* yd = reinterpret_cast<unsigned*>(
+                    reinterpret_cast<char*>(kv + (li + 1) * lstride + (size_t)tile0 * max_pos * kE) +
+                    yq_row_offset(pos, t, TILE, max_pos) + 12 * (j >> 2) + 4 * k);
+                if (tile0 + t < N && k < 3) {
+                    if (pos < lpin(li + 1)) *yd = word;
+                    else __builtin_nontemporal_store(word, yd);
+                }
+            } else if (L0R && !last) {  // block li+1's y at `pos`: its K/V-cache row (128 B per half-wave)
                 S.kcur[t][j] = y;
                 const int task = tile0 + t;
                 float* yd = kv + (li + 1) * lstride + ((size_t)tile0 * max_pos + (size_t)pos * TILE + t) * kE + j;
@@ -1266,8 +1335,9 @@ __device__ inline int select_rollout(const float* logits, int A, int sample, dou
 
 // The bandit online loop (evals/eval_bandit.py:70-89) for one tile of tasks,
 // all H steps: decode -> select -> env step -> append transition.
-template <int TILE, bool GL, int L0M = 0>
-__global__ __launch_bounds__(TILE * 64, 4) void rollout_bandit_kernel(ModelView M, BanditRolloutParams Pr) {
+// YQ: the packed 24-bit y cache (rollout_bandit_kernel); otherwise fp32 rows (rollout_bandit_f32_kernel)
+template <int TILE, bool GL, int L0M, bool YQ>
+__device__ __attribute__((always_inline)) inline void rollout_bandit_body(const ModelView& M, const BanditRolloutParams& Pr) {
     DPT_SMEM_SETUP(TILE)
     const int tile0 = blockIdx.x * TILE;
     const int tid = threadIdx.x;
@@ -1287,15 +1357,17 @@ __global__ __launch_bounds__(TILE * 64, 4) void rollout_bandit_kernel(ModelView 
         const float acc = (k < A) ? (ew[j] + ew[(1 + k) * kE + j]) + ew[(1 + A) * kE + j] : ew[j];
         D[rl.base + i] = acc + P[pl.emb_b + j];
     }
+    // the packed cache runs on the second set of folded weights (ln_1's g and b folded in)
+    const float* l0w = M.l0 + (YQ ? (size_t)M.n_layer * L0Off::size : 0);
     for (int i = tid; i < M.n_layer * kE; i += TILE * 64) {
         const int li = i / kE, j = i % kE;
-        D[rl.g0 + i] = M.l0[(size_t)li * L0Off::size + L0Off::g0 + j];
-        D[rl.bvp + i] = M.l0[(size_t)li * L0Off::size + L0Off::bvp + j];
+        D[rl.g0 + i] = l0w[(size_t)li * L0Off::size + L0Off::g0 + j];
+        D[rl.bvp + i] = l0w[(size_t)li * L0Off::size + L0Off::bvp + j];
     }
     for (int i = tid; i < M.n_layer * kE * kE; i += TILE * 64) {
         const int li = i / (kE * kE), j = i % (kE * kE);
-        D[rl.wvp + i] = M.l0[(size_t)li * L0Off::size + L0Off::Wvp + j];
-        if (GL) D[rl.G + i] = M.l0[(size_t)li * L0Off::size + L0Off::G + j];
+        D[rl.wvp + i] = l0w[(size_t)li * L0Off::size + L0Off::Wvp + j];
+        if (GL) D[rl.G + i] = l0w[(size_t)li * L0Off::size + L0Off::G + j];
     }
     if constexpr (L0M > 0) {
         // l0_tiles' constants as maps of xn: column c of gx is G v_c and gx0[c] = g0 . v_c for
@@ -1341,7 +1413,7 @@ __global__ __launch_bounds__(TILE * 64, 4) void rollout_bandit_kernel(ModelView 
             const doublex2 d2 = __builtin_nontemporal_load(reinterpret_cast<const doublex2*>(draws + (size_t)h * TILE));
             dr = make_double2(d2[0], d2[1]);
         }
-        decode_position<TILE, true, GL, L0M>(S, P, pl, M, Pr.kv, Pr.N, Pr.H, tile0, h, wpe_j, D, Pr.pin, Pr.pin_x);
+        decode_position<TILE, true, GL, L0M, YQ>(S, P, pl, M, Pr.kv, Pr.N, Pr.H, tile0, h, wpe_j, D, Pr.pin, Pr.pin_x);
         // selection + env step; the outputs are stored after the barrier so that it
         // waits only for the y rows (issued phases earlier), not for these stores
         const int t = tid, task = tile0 + t;
@@ -1372,6 +1444,18 @@ __global__ __launch_bounds__(TILE * 64, 4) void rollout_bandit_kernel(ModelView 
     }
 }
 
+// the default: blocks >= 1 cache packed 24-bit rows (DPT_TUNE_YCACHE_BITS = 24)
+template <int TILE, bool GL, int L0M = 0>
+__global__ __launch_bounds__(TILE * 64, 4) void rollout_bandit_kernel(ModelView M, BanditRolloutParams Pr) {
+    rollout_bandit_body<TILE, GL, L0M, true>(M, Pr);
+}
+
+// fp32 rows (DPT_TUNE_YCACHE_BITS = 32: the comparison path; and block 0 on the matrix cores)
+template <int TILE, bool GL, int L0M = 0>
+__global__ __launch_bounds__(TILE * 64, 4) void rollout_bandit_f32_kernel(ModelView M, BanditRolloutParams Pr) {
+    rollout_bandit_body<TILE, GL, L0M, false>(M, Pr);
+}
+
 // ----------------------------------------------------------------------------- host side
 
 ModelView make_view(const float* blob, const dpt_model_desc& d) {
@@ -1399,37 +1483,54 @@ ModelView make_view(const float* blob, const dpt_model_desc& d) {
 }
 
 // ModelView::l0 from every block's weights (fp64 sums, one rounding per
-// element); workgroup li derives block li.
+// element); workgroup (li, s) derives block li of set s.  Set 0 is the plain fold.  Set 1 (n_layer
+// blocks after set 0; the rollout's packed y cache, which stores yhat = (h - mean) rstd of ln_1
+// without its g and b) folds them in for blocks >= 1: G' = G diag(g), g0' = g0 * g, Wvp' = diag(g) Wvp,
+// bvp' = b Wvp + bvp; its block 0 (no y cache) equals set 0's.
 __global__ void derive_l0_kernel(ModelView M, float* __restrict__ l0_all) {
     const float* W = M.layers + (size_t)blockIdx.x * LayerOff::size;
-    float* l0 = l0_all + (size_t)blockIdx.x * L0Off::size;
+    float* l0 = l0_all + ((size_t)blockIdx.y * M.n_layer + blockIdx.x) * L0Off::size;
+    const bool fold = blockIdx.y == 1 && blockIdx.x >= 1;
     const float* aw = W + LayerOff::attn_w;  // [E][3E]: q | k | v columns
     const float* ab = W + LayerOff::attn_b;
     const float* pw = W + LayerOff::proj_w;  // [E][E]
+    const float* lg = W + LayerOff::ln1_g;
+    const float* lb = W + LayerOff::ln1_b;
+    // Wvp[m][n] = sum_j Wv[m][j] Wproj[j][n]
+    auto wvp = [&](int m, int n) {
+        double acc = 0.0;
+        for (int j = 0; j < kE; ++j) acc += (double)aw[m * 3 * kE + 2 * kE + j] * (double)pw[j * kE + n];
+        return acc;
+    };
     for (int i = threadIdx.x; i < L0Off::size; i += blockDim.x) {
         double acc = 0.0;
         if (i < L0Off::g0) {  // G[m][n] = sum_j Wq[m][j] Wk[n][j]
             const int m = i / kE, n = i % kE;
             for (int j = 0; j < kE; ++j) acc += (double)aw[m * 3 * kE + j] * (double)aw[n * 3 * kE + kE + j];
+            if (fold) acc *= (double)lg[n];
         } else if (i < L0Off::Wvp) {  // g0[n] = sum_j Wk[n][j] bq[j]
             const int n = i - L0Off::g0;
             for (int j = 0; j < kE; ++j) acc += (double)aw[n * 3 * kE + kE + j] * (double)ab[j];
-        } else if (i < L0Off::bvp) {  // Wvp[m][n] = sum_j Wv[m][j] Wproj[j][n]
+            if (fold) acc *= (double)lg[n];
+        } else if (i < L0Off::bvp) {
             const int m = (i - L0Off::Wvp) / kE, n = (i - L0Off::Wvp) % kE;
-            for (int j = 0; j < kE; ++j) acc += (double)aw[m * 3 * kE + 2 * kE + j] * (double)pw[j * kE + n];
+            acc = wvp(m, n);
+            if (fold) acc *= (double)lg[m];
         } else {  // bvp[n] = sum_j bv[j] Wproj[j][n] + bproj[n]
             const int n = i - L0Off::bvp;
             for (int j = 0; j < kE; ++j) acc += (double)ab[2 * kE + j] * (double)pw[j * kE + n];
             acc += (double)W[LayerOff::proj_b + n];
+            if (fold)
+                for (int m = 0; m < kE; ++m) acc += (double)lb[m] * wvp(m, n);
         }
         l0[i] = (float)acc;
     }
 }
 
-int64_t l0_numel(int n_layer) { return (int64_t)n_layer * L0Off::size; }
+int64_t l0_numel(int n_layer) { return (int64_t)2 * n_layer * L0Off::size; }
 
 int launch_derive_l0(const ModelView& M, float* l0, hipStream_t st) {
-    hipLaunchKernelGGL(derive_l0_kernel, dim3(M.n_layer), dim3(256), 0, st, M, l0);
+    hipLaunchKernelGGL(derive_l0_kernel, dim3(M.n_layer, 2), dim3(256), 0, st, M, l0);
     return check_hip(hipGetLastError(), "derive_l0_kernel launch");
 }
 
@@ -1454,6 +1555,13 @@ extern "C" int dpt_debug_stamps(unsigned long long* out, int n, int reset) {
 static int g_decode_tile = 8;  // tuning knob (dpt_tuning_set(DPT_TUNE_DECODE_TILE, 8|16))
 static int64_t g_cache_budget = DPT_DEFAULT_CACHE_BUDGET;  // DPT_TUNE_CACHE_BUDGET
 static bool g_block0_mfma = false;                         // DPT_TUNE_BLOCK0_MFMA
+static int g_ycache_bits = 24;                             // DPT_TUNE_YCACHE_BITS
+
+int set_ycache_bits(int bits) {
+    if (bits != 24 && bits != 32) return DPT_EINVAL;
+    g_ycache_bits = bits;
+    return DPT_OK;
+}
 
 int set_block0_mfma(int on) {
     g_block0_mfma = on != 0;
@@ -1472,9 +1580,10 @@ int set_cache_budget(int64_t b) {
 // across steps; the rest stream non-temporally and do not displace them.  The
 // budget is spent in whole stream chunks (8 kYRows positions of one block): every
 // block gets `pin` positions and blocks 1..pin_x one chunk more.
-static void rollout_pin(int N, int H, int n_layer, int* pin, int* pin_x) {
+static void rollout_pin(int N, int H, int n_layer, bool packed, int* pin, int* pin_x) {
     constexpr int chunk = 8 * kYRows;
-    const int64_t row = (int64_t)N * kE * sizeof(float);  // one position of one block, all tasks
+    // one position of one block, all tasks
+    const int64_t row = (int64_t)N * (packed ? (int64_t)kYqRowBytes : (int64_t)(kE * sizeof(float)));
     const int64_t nb = n_layer - 1;                          // blocks with a y cache
     *pin = 0;
     *pin_x = 0;
@@ -1568,7 +1677,10 @@ int launch_rollout_bandit(const ModelView& M, const dpt_bandit_rollout_args& a, 
     P.logits_out = a.logits_out;
     P.n_layer = M.n_layer;
     P.tile = g_decode_tile;
-    rollout_pin(a.N, a.H, M.n_layer, &P.pin, &P.pin_x);
+    // the packed 24-bit y cache unless the fp32 form is asked for; block 0 on the matrix cores is
+    // built in the fp32 form only
+    const bool packed = g_ycache_bits == 24 && !l0m;
+    rollout_pin(a.N, a.H, M.n_layer, packed, &P.pin, &P.pin_x);
     const int64_t nd = (int64_t)a.N * a.H;
     hipLaunchKernelGGL(rollout_draws_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, P);
     auto launch = [&](auto kernel, int tile) {
@@ -1576,7 +1688,11 @@ int launch_rollout_bandit(const ModelView& M, const dpt_bandit_rollout_args& a, 
         hipLaunchKernelGGL(kernel, dim3((a.N + tile - 1) / tile), dim3(tile * 64), sm, st, M, P);
     };
     if (l0m)
-        gl ? launch(rollout_bandit_kernel<8, true, 6>, 8) : launch(rollout_bandit_kernel<8, false, 6>, 8);
+        gl ? launch(rollout_bandit_f32_kernel<8, true, 6>, 8) : launch(rollout_bandit_f32_kernel<8, false, 6>, 8);
+    else if (!packed && g_decode_tile == 8)
+        gl ? launch(rollout_bandit_f32_kernel<8, true>, 8) : launch(rollout_bandit_f32_kernel<8, false>, 8);
+    else if (!packed)
+        gl ? launch(rollout_bandit_f32_kernel<16, true>, 16) : launch(rollout_bandit_f32_kernel<16, false>, 16);
     else if (g_decode_tile == 8)
         gl ? launch(rollout_bandit_kernel<8, true>, 8) : launch(rollout_bandit_kernel<8, false>, 8);
     else

@@ -413,6 +413,12 @@ def set_cache_budget(nbytes):
     _lib.call("dpt_tuning_set", _lib.TUNE_CACHE_BUDGET, int(nbytes))
 
 
+def set_ycache_bits(bits):
+    """Bandit rollout: storage of the cached ln_1 rows of blocks >= 1, 24 (default: 24-bit fixed
+    point, 96 B per position) or 32 (fp32, 128 B: the comparison path)."""
+    _lib.call("dpt_tuning_set", _lib.TUNE_YCACHE_BITS, int(bits))
+
+
 def set_block0_mfma(on):
     """Bandit rollout, 5 arms at tile 8: block 0's attention on the matrix cores, or one wave per
     task on the vector ALUs (default).  Same algebra; the fp32 summation order differs."""

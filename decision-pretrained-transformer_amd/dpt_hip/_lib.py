@@ -159,6 +159,7 @@ TUNE_CACHE_BUDGET = 4
 TUNE_BLOCK0_MFMA = 5
 TUNE_SELECT_FAST = 6
 TUNE_POLICY_WAVE = 7
+TUNE_YCACHE_BITS = 8
 SIGNATURES["dpt_tuning_set"] = (_i32, [_i32, _i64])
 
 

@@ -43,7 +43,8 @@ extern "C" {
  * (dpt_interactive_pack, dpt_train_ce_last, dpt_interactive_workspace_numel, dpt_interactive_grad)
  * and DPT_BANDIT_F32 in dpt_rollout_bandit_generic; the explorer/exploiter training step
  * (dpt_rollout_bandit_generic_env, DPT_STREAM_ENVACT, dpt_train_ce_rows, dpt_explore_weights,
- * dpt_explore_workspace_numel, dpt_explore_grad) */
+ * dpt_explore_workspace_numel, dpt_explore_grad); the tuning key DPT_TUNE_YCACHE_BITS (dpt_rollout_bandit
+ * caches its rows as 24-bit fixed point by default; no struct or signature changed) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -101,7 +102,13 @@ const char* dpt_last_error(void);
  * DPT_TUNE_POLICY_WAVE = 1 (the only value): dpt_rollout_policy runs one 64-lane
  * workgroup per task with the task's context in LDS (the per-arm pairwise sums
  * split over lanes in numpy's order); 0 returns DPT_EUNSUPPORTED since round 6
- * (the lane-per-task kernel was retired).  */
+ * (the lane-per-task kernel was retired).
+ * DPT_TUNE_YCACHE_BITS = 24 (default): dpt_rollout_bandit caches the normalised
+ * ln_1 rows of blocks >= 1 as signed 24-bit fixed point (96 B per position,
+ * absolute error <= 2^-21, below the kernel's fp32 summation noise; ln_1's g and b
+ * are folded into the derived weights); 32: as fp32 rows (128 B), the comparison
+ * path.  Block 0 on the matrix cores (DPT_TUNE_BLOCK0_MFMA = 1) always runs the
+ * fp32 form.  The workspace size (dpt_kvcache_numel) is the same for both.  */
 #define DPT_TUNE_DECODE_TILE 1
 #define DPT_TUNE_PREFILL 2
 #define DPT_TUNE_DARKROOM_MEMO 3
@@ -109,6 +116,7 @@ const char* dpt_last_error(void);
 #define DPT_TUNE_BLOCK0_MFMA 5
 #define DPT_TUNE_SELECT_FAST 6
 #define DPT_TUNE_POLICY_WAVE 7
+#define DPT_TUNE_YCACHE_BITS 8
 int dpt_tuning_set(int32_t key, int64_t value);
 /* number of visible gfx950 devices (0 on a CPU-only host; never faults) */
 int dpt_device_count(int* count_out_host);

@@ -2,7 +2,8 @@
 each in its own process (python scripts/ab_lib.py libA.so libB.so ...; rounds alternate).
 An argument libX.so:<bytes> runs libX.so with dpt_hip.set_cache_budget(<bytes>); a suffix +b0 / +nob0
 runs it with dpt_hip.set_block0_mfma(True / False); +nows / +nomemo run DarkRoom without the
-layer-0 workspace / the logits memo (suffixes in that order: lib.so+nows+nomemo).
+layer-0 workspace / the logits memo (suffixes in that order: lib.so+nows+nomemo); a last suffix
++y32 / +y24 sets dpt_hip.set_ycache_bits (a build without that key fails when it is set).
 Env: AB_H, AB_N, AB_A, AB_TILE, AB_ROUNDS."""
 import json
 import os
@@ -17,6 +18,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def child(lib):
     sys.path[:0] = [os.path.join(ROOT, "decision-pretrained-transformer_amd"), ROOT]
     from dpt_hip import _lib
+    ybits = None  # "libX.so+y32" / "+y24": DPT_TUNE_YCACHE_BITS (the last suffix)
+    for suf, bits in (("+y32", 32), ("+y24", 24)):
+        if lib.endswith(suf):
+            lib, ybits = lib[: -len(suf)], bits
     b0 = None  # "libX.so+b0" / "+nob0": DPT_TUNE_BLOCK0_MFMA 1 / 0
     for suf, on in (("+nob0", False), ("+b0", True)):
         if lib.endswith(suf):
@@ -33,6 +38,8 @@ def child(lib):
     dpt_hip.set_decode_tile(int(os.environ.get("AB_TILE", "8")))
     if b0 is not None:
         dpt_hip.set_block0_mfma(b0)
+    if ybits is not None:
+        dpt_hip.set_ycache_bits(ybits)
     if nomemo:
         dpt_hip.set_darkroom_memo(False)
     if nows:
@@ -100,6 +107,7 @@ if __name__ == "__main__":
     sys.path[:0] = [ROOT]
     import bench
     ab = bench.algorithmic_bytes(N, H, 4)
-    print(json.dumps({lib: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)),
+    print(json.dumps({lib: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v)),
+                            "ms": [round(float(x), 4) for x in v],
                             "TBps": ab / (np.median(v) * 1e-3) / 1e12, "checksum": chk[lib]}
                       for lib, v in res.items()}))
