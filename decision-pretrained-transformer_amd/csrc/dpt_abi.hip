@@ -72,14 +72,27 @@ int set_select_fast(int);
 int regret_max_steps();
 int64_t regret_workspace_numel(int N, int H);
 int launch_regret_moments(const double*, const double*, int, int, int, const double*, double*, double*, hipStream_t);
-int train_forward(const TrDims&, const float*, const float*, float*, float*, hipStream_t);
-int train_backward(const TrDims&, const float*, const float*, float*, const float*, float*, hipStream_t);
+int train_forward(const TrDims&, const float*, const float*, float*, float*, hipStream_t,
+                  const float* embeds = nullptr);
+int train_backward(const TrDims&, const float*, const float*, float*, const float*, float*, hipStream_t,
+                   float* dembeds = nullptr);
 int64_t train_workspace_numel(const TrDims&);
 int64_t train_blob_numel(const TrDims&);
 int train_dims_check(const TrDims&);
 int64_t gen_rollout_workspace_numel(const TrDims&, int, int);
 int rollout_bandit_generic(const TrDims&, const float*, const dpt_bandit_rollout_args&, hipStream_t,
                            const GenEnvAct* env = nullptr);
+
+
+void drop_params(float p, uint32_t& thr, float& scale) {
+    thr = 0u;
+    scale = 1.0f;
+    if (p > 0.0f) {  // keep iff word >= ceil(p 2^32): P(keep) = 1 - p to 2^-32
+        const double t = std::ceil((double)p * 4294967296.0);
+        thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+        scale = 1.0f / (1.0f - p);
+    }
+}
 
 }  // namespace dpt
 
@@ -534,11 +547,7 @@ static int train_dims(const dpt_train_desc* d, TrDims& o) {
     const int fo = (d->reserved & DPT_TRAIN_FORWARD_ONLY) ? ((d->reserved & DPT_TRAIN_LAST_ONLY) ? 3 : 1) : 0;
     o = TrDims{d->n_layer, d->n_embd, 2 * d->state_dim + d->action_dim + 1, d->action_dim, d->batch, d->window,
                d->n_positions, fo, 0u, 1.0f, d->dropout_seed, (d->reserved & DPT_TRAIN_LAST_LOSS) ? 1 : 0};
-    if (d->dropout > 0.0f) {  // keep iff word >= ceil(p 2^32): P(keep) = 1 - p to 2^-32
-        const double t = std::ceil((double)d->dropout * 4294967296.0);
-        o.drop_thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
-        o.drop_scale = 1.0f / (1.0f - d->dropout);
-    }
+    drop_params(d->dropout, o.drop_thr, o.drop_scale);
     return train_dims_check(o);
 }
 
@@ -573,6 +582,23 @@ int dpt_train_backward(const dpt_train_desc* d, const float* blob, const float* 
     REQUIRE(blob && tokens && ws && dpreds && dblob, "null pointer");
     REQUIRE(!t.fwd_only, "train backward: the description is forward-only (DPT_TRAIN_FORWARD_ONLY)");
     return train_backward(t, blob, tokens, ws, dpreds, dblob, S(stream));
+}
+
+int dpt_train_forward_embeds(const dpt_train_desc* d, const float* blob, const float* embeds, float* ws,
+                             float* preds, void* stream) {
+    TrDims t;
+    if (int rc = train_dims(d, t)) return rc;
+    REQUIRE(blob && embeds && ws && preds, "train forward (embeds): null pointer");
+    return train_forward(t, blob, nullptr, ws, preds, S(stream), embeds);
+}
+
+int dpt_train_backward_embeds(const dpt_train_desc* d, const float* blob, float* ws, const float* dpreds,
+                              float* dblob, float* dembeds, void* stream) {
+    TrDims t;
+    if (int rc = train_dims(d, t)) return rc;
+    REQUIRE(blob && ws && dpreds && dblob && dembeds, "train backward (embeds): null pointer");
+    REQUIRE(!t.fwd_only, "train backward (embeds): the description is forward-only (DPT_TRAIN_FORWARD_ONLY)");
+    return train_backward(t, blob, nullptr, ws, dpreds, dblob, S(stream), dembeds);
 }
 
 int dpt_rollout_bandit_generic_workspace_numel(const dpt_train_desc* d, int32_t N, int32_t H, int64_t* numel) {

@@ -322,6 +322,36 @@ struct TrDims {
     __host__ __device__ int64_t layer_size() const { return 12ll * E * E + 13ll * E; }
 };
 
+// dropout factor of element e of a site (dpt_hip.h dpt_train_desc): drop_scale when the element's
+// Philox word clears the threshold, else 0.  Regenerated in the backward -- no mask is stored.
+__device__ inline float tr_keep(const TrDims& d, int site, int64_t e) {
+    const U4 r = philox(d.drop_seed, (uint64_t)site, e >> 2, DPT_STREAM_DROPOUT);
+    const int k = (int)(e & 3);
+    const uint32_t w = k == 0 ? r.x : k == 1 ? r.y : k == 2 ? r.z : r.w;
+    return w >= d.drop_thr ? d.drop_scale : 0.0f;
+}
+
+// dropout p -> (drop_thr, drop_scale) of TrDims (defined in dpt_abi.hip): keep iff word >= ceil(p 2^32)
+void drop_params(float p, uint32_t& thr, float& scale);
+
+// The training row kernels of dpt_train.hip as host entry points for the image front end
+// (dpt_image.hip): Y = X W + bias, LayerNorm forward / input gradient / parameter gradients, the
+// chunked weight gradient with its fixed-order reduction, and dX = dY W^T.  `part` is scratch of
+// rows_chunks(R) * (IN + 1) * OUT floats (rows_ln_param_grad: IN = 1, OUT = E).
+int64_t rows_chunks(int64_t R);
+int rows_linear(const float* X, const float* W, const float* bias, int R, int IN, int OUT, float* Y, hipStream_t st);
+int rows_layernorm(const float* x, const float* g, const float* b, int R, int E, float* y, float* stats,
+                   hipStream_t st);
+int rows_layernorm_bwd(const float* x, const float* stats, const float* g, const float* dy, int R, int E, float* dx,
+                       hipStream_t st);
+int rows_ln_param_grad(const float* x, const float* stats, const float* dy, int R, int E, float* part, float* dg,
+                       float* db, hipStream_t st);
+int rows_wgrad(const float* X, const float* dY, int R, int IN, int OUT, float* part, float* dW, float* db,
+               hipStream_t st);
+int rows_linear_bwd_data(const float* dY, const float* W, int R, int IN, int OUT, float* dX, hipStream_t st);
+// dW (IN x OUT) | db (OUT) = nch partials of (IN + 1) * OUT floats summed in chunk order (tr_wgrad_reduce)
+int rows_reduce_parts(const float* part, int nch, int IN, int OUT, float* dW, float* db, hipStream_t st);
+
 // The env action of rollout_bandit_generic when it is not the action written into the context
 // (dpt_rollout_bandit_generic_env, dpt_explore.hip): the reward and arm_value_out come from it.
 struct GenEnvAct {

@@ -145,13 +145,15 @@ __global__ void tr_embed(const float* __restrict__ tok, const float* __restrict_
     x[i] = acc + blob[b.wpe + (int64_t)t * d.E + e];
 }
 
-// dropout factor of element e of a site (dpt_hip.h dpt_train_desc): drop_scale when the element's
-// Philox word clears the threshold, else 0.  Regenerated in the backward -- no mask is stored.
-__device__ inline float tr_keep(const TrDims& d, int site, int64_t e) {
-    const U4 r = philox(d.drop_seed, (uint64_t)site, e >> 2, DPT_STREAM_DROPOUT);
-    const int k = (int)(e & 3);
-    const uint32_t w = k == 0 ? r.x : k == 1 ? r.y : k == 2 ? r.z : r.w;
-    return w >= d.drop_thr ? d.drop_scale : 0.0f;
+// (tr_keep, the dropout factor of one element of a site, lives in dpt_common.h)
+
+// x[r][e] = embeds[r][e] + wpe[t]: the token embedding computed by the caller (dpt_train_forward_embeds)
+__global__ void tr_embed_in(const float* __restrict__ embeds, const float* __restrict__ blob, TrDims d, TrBlob b,
+                            float* __restrict__ x) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)d.R() * d.E) return;
+    const int e = (int)(i % d.E), t = (int)(i / d.E) % d.T;
+    x[i] = embeds[i] + blob[b.wpe + (int64_t)t * d.E + e];
 }
 
 // out[i] = (add ? add[i] : 0) + x[i] keep(site, i) over n elements: the dropout of the embedding
@@ -924,6 +926,43 @@ static int ln_param_grad(const float* x, const float* stt, const float* dy, int 
     return launched("tr_ln_param");
 }
 
+// ---- the row kernels as host entry points (dpt_common.h; the image front end, dpt_image.hip)
+int64_t rows_chunks(int64_t R) { return (R + kTrRowsPerChunk - 1) / kTrRowsPerChunk; }
+int rows_linear(const float* X, const float* W, const float* bias, int R, int IN, int OUT, float* Y, hipStream_t st) {
+    hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)R * OUT)), dim3(kTrThreads), 0, st, X, W, bias,
+                       (const float*)nullptr, R, IN, OUT, 0, Y);
+    return launched("tr_linear");
+}
+int rows_layernorm(const float* x, const float* g, const float* b, int R, int E, float* y, float* stats,
+                   hipStream_t st) {
+    layernorm(x, g, b, R, E, y, stats, st);
+    return launched("tr_layernorm");
+}
+int rows_layernorm_bwd(const float* x, const float* stats, const float* g, const float* dy, int R, int E, float* dx,
+                       hipStream_t st) {
+    const int rows_per_block = kTrThreads / 64;
+    hipLaunchKernelGGL(tr_layernorm_bwd, dim3((R + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), 0, st, x,
+                       stats, g, dy, R, E, (const float*)nullptr, dx);
+    return launched("tr_layernorm_bwd");
+}
+int rows_ln_param_grad(const float* x, const float* stats, const float* dy, int R, int E, float* part, float* dg,
+                       float* db, hipStream_t st) {
+    return ln_param_grad(x, stats, dy, R, E, part, dg, db, st);
+}
+int rows_wgrad(const float* X, const float* dY, int R, int IN, int OUT, float* part, float* dW, float* db,
+               hipStream_t st) {
+    return wgrad(X, dY, R, IN, OUT, 0, part, dW, db, st);
+}
+int rows_linear_bwd_data(const float* dY, const float* W, int R, int IN, int OUT, float* dX, hipStream_t st) {
+    hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for((int64_t)R * IN)), dim3(kTrThreads), 0, st, dY, W, R, IN,
+                       OUT, (const float*)nullptr, (const float*)nullptr, dX);
+    return launched("tr_linear_bwd_data");
+}
+int rows_reduce_parts(const float* part, int nch, int IN, int OUT, float* dW, float* db, hipStream_t st) {
+    reduce_parts(part, nch, IN, OUT, dW, db, st);
+    return launched("tr_wgrad_reduce");
+}
+
 // ---- matrix-core dispatch (widths 16, 32, 64; other widths keep the row kernels)
 static bool mm_fast(int E) { return E == 16 || E == 32 || E == 64; }
 enum MmKind { kMmQkv, kMmProj, kMmFc, kMmMp, kMmBdMp, kMmBdFc, kMmBdProj, kMmBdQkv, kMmU, kMmLnQkv, kMmLnFc };
@@ -1164,7 +1203,9 @@ __global__ void tr_last_rows(const float* __restrict__ src, float* __restrict__ 
     else dst[i] = src[r];
 }
 
-int train_forward(const TrDims& d, const float* blob, const float* tok, float* ws, float* preds, hipStream_t st) {
+// embeds != nullptr (dpt_train_forward_embeds): x0 = drop(embeds + wpe[t]); tok and the blob's emb_w / emb_b are not read
+int train_forward(const TrDims& d, const float* blob, const float* tok, float* ws, float* preds, hipStream_t st,
+                  const float* embeds) {
     if (int rc = train_dims_check(d)) return rc;
     const TrBlob B = TrBlob::make(d);
     const TrWs W = TrWs::make(d);
@@ -1177,7 +1218,10 @@ int train_forward(const TrDims& d, const float* blob, const float* tok, float* w
         return DPT_EUNSUPPORTED;
     }
     if (attn_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds);
-    hipLaunchKernelGGL(tr_embed, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, tok, blob, d, B, ws + W.x);
+    if (embeds)
+        hipLaunchKernelGGL(tr_embed_in, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, embeds, blob, d, B, ws + W.x);
+    else
+        hipLaunchKernelGGL(tr_embed, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, tok, blob, d, B, ws + W.x);
     // dropout (GPT2Model in training mode): drop(x0) in place, the attention probabilities, and
     // c_proj / mlp.c_proj outputs before their residual adds -- on the row kernels, which take the
     // masks (the matrix-core forms fuse the residual add)
@@ -1441,8 +1485,10 @@ static int train_backward_last_top(const TrDims& d, const TrBlob& B, const TrWs&
     return launched("train backward (last-position loss)");
 }
 
+// dembeds != nullptr (dpt_train_backward_embeds): dL/dx0 after the site-0 mask goes to dembeds (R, E) and the
+// emb_w / emb_b gradient stays the memset's exact zeros; tok is not read
 int train_backward(const TrDims& d, const float* blob, const float* tok, float* ws, const float* dpreds,
-                   float* dblob, hipStream_t st) {
+                   float* dblob, hipStream_t st, float* dembeds) {
     if (int rc = train_dims_check(d)) return rc;
     const TrBlob B = TrBlob::make(d);
     const TrWs W = TrWs::make(d);
@@ -1558,7 +1604,13 @@ int train_backward(const TrDims& d, const float* blob, const float* tok, float* 
     }
     // embedding: x0 = drop(tok emb_w + emb_b + wpe[t])
     if (drop) hipLaunchKernelGGL(tr_dropout, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dx, nullptr, RE, d, 0, dx);
-    if (int rc = wgrad(tok, dx, R, d.F, E, 0, part, dblob + B.emb_w, dblob + B.emb_b, st)) return rc;
+    if (dembeds) {
+        if (int rc = check_hip(hipMemcpyAsync(dembeds, dx, sizeof(float) * RE, hipMemcpyDeviceToDevice, st),
+                               "dembeds copy"))
+            return rc;
+    } else if (int rc = wgrad(tok, dx, R, d.F, E, 0, part, dblob + B.emb_w, dblob + B.emb_b, st)) {
+        return rc;
+    }
     hipLaunchKernelGGL(tr_wpe_grad, dim3(blocks_for((int64_t)d.T * E)), dim3(kTrThreads), 0, st, dx, d, dblob + B.wpe);
     return launched("train backward embed");
 }

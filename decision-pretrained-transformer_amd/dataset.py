@@ -9,7 +9,11 @@ permuted by one ``torch.randperm(horizon)``).
 ``(index, torch.randperm(horizon))`` with ``shuffle``, so a ``DataLoader`` over it draws from the
 CPU generator exactly what a loader over the ``Dataset`` draws (the sampler's order, then one
 permutation per item in batch order) while the samples themselves stay on the device, where
-dpt_train_pack_batch gathers them.  ImageDataset (miniworld) is out of scope.
+dpt_train_pack_batch gathers them.
+
+``ImageDataset`` is the reference's dataset.py:94-145 for image-based (miniworld) data collected
+elsewhere: the same constructor and item dict, each item's ``context_images`` read from its ``.npy``
+stack, and ``image_transform`` restating the reference's ``ToTensor`` + ``Normalize`` pair.
 """
 import pickle
 
@@ -76,3 +80,47 @@ class IndexView(torch.utils.data.Dataset):
         if self.dataset.shuffle:
             return index, torch.randperm(self.dataset.horizon)
         return index
+
+
+_IMAGE_MEAN = (0.485, 0.456, 0.406)  # train.py:224-228: the ImageNet statistics
+_IMAGE_STD = (0.229, 0.224, 0.225)
+
+
+def image_transform(pic):
+    """train.py:224-228 ``Compose([ToTensor(), Normalize(mean, std)])`` for the float HWC arrays in
+    [0, 1] the collected data holds (``skimage.resize`` output): ``ToTensor`` only permutes a float
+    array to CHW, ``Normalize`` computes (x - mean) / std in the array's own dtype (float64)."""
+    t = torch.from_numpy(np.ascontiguousarray(np.asarray(pic).transpose(2, 0, 1)))
+    if not t.is_floating_point():
+        raise TypeError("image_transform: expected a float image in [0, 1]")
+    mean = torch.as_tensor(_IMAGE_MEAN, dtype=t.dtype)[:, None, None]
+    std = torch.as_tensor(_IMAGE_STD, dtype=t.dtype)[:, None, None]
+    return (t - mean) / std
+
+
+class ImageDataset(Dataset):
+    """Dataset class for image-based data (dataset.py:94-145)."""
+
+    def __init__(self, paths, config, transform=image_transform):
+        config["store_gpu"] = False
+        super().__init__(paths, config)
+        self.transform = transform
+        self.config = config
+        self.dataset.update({
+            "context_filepaths": [traj["context_images"] for traj in self.trajs],
+            "query_images": torch.stack([self.transform(traj["query_image"]).float() for traj in self.trajs]),
+        })
+
+    def __getitem__(self, index):
+        context_images = np.load(self.dataset["context_filepaths"][index])
+        context_images = torch.stack([self.transform(images) for images in context_images]).float()
+        res = {"context_images": context_images}
+        res.update({k: self.dataset[k][index] for k in _CONTEXT})
+        res.update({"query_images": self.dataset["query_images"][index],
+                    "query_states": self.dataset["query_states"][index],
+                    "optimal_actions": self.dataset["optimal_actions"][index], "zeros": self.zeros})
+        if self.shuffle:
+            perm = torch.randperm(self.horizon)
+            for k in ("context_images",) + _CONTEXT:
+                res[k] = res[k][perm]
+        return res

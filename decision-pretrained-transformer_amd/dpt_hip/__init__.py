@@ -73,6 +73,47 @@ def pack_weights(sd, n_layer):
     return torch.cat([p.contiguous().reshape(-1) for p in parts])
 
 
+# the image front end's parameters in front-blob order (dpt_hip.h dpt_image_desc); the two nn.Linear
+# weights are stored [in][out] in the blob
+FRONT_KEYS = ("image_encoder.0.weight", "image_encoder.0.bias", "image_encoder.2.weight", "image_encoder.2.bias",
+              "image_encoder.6.weight", "image_encoder.6.bias", "embed_transition.weight", "embed_transition.bias",
+              "embed_ln.weight", "embed_ln.bias")
+_FRONT_LINEAR = ("image_encoder.6.weight", "embed_transition.weight")
+
+
+def pack_front(sd):
+    """Flatten the front-end entries of an ``ImageTransformer.state_dict()`` (or any mapping with
+    those keys) into the front blob, on the device of its tensors."""
+    def t(k):
+        v = sd[k]
+        v = v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(v)
+        v = v.to(torch.float32)
+        return v.t() if k in _FRONT_LINEAR else v
+
+    return torch.cat([t(k).contiguous().reshape(-1) for k in FRONT_KEYS])
+
+
+def unpack_front(blob, state_dim, action_dim, n_embd):
+    """The inverse of ``pack_front``: {key: tensor shaped like the module's parameter} (views of
+    ``blob``; the two nn.Linear weights come back transposed to torch's [out][in])."""
+    F = 8 + state_dim + action_dim + 1
+    shapes = {"image_encoder.0.weight": (16, 3, 3, 3), "image_encoder.0.bias": (16,),
+              "image_encoder.2.weight": (16, 16, 3, 3), "image_encoder.2.bias": (16,),
+              "image_encoder.6.weight": (8, 1600), "image_encoder.6.bias": (8,),
+              "embed_transition.weight": (n_embd, F), "embed_transition.bias": (n_embd,),
+              "embed_ln.weight": (n_embd,), "embed_ln.bias": (n_embd,)}
+    out, off = {}, 0
+    for k in FRONT_KEYS:
+        sh = shapes[k]
+        n = int(np.prod(sh))
+        flat = blob[off:off + n]
+        out[k] = flat.view(sh[1], sh[0]).t() if k in _FRONT_LINEAR else flat.view(sh)
+        off += n
+    if off != blob.numel():
+        raise ValueError(f"front blob {blob.numel()} != parameters {off}")
+    return out
+
+
 class DeviceModel:
     """Owns one ``dpt_model`` handle (the packed fp32 weights on the GPU)."""
 

@@ -275,3 +275,24 @@ SIGNATURES["dpt_train_ce_rows"] = (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_vo
 SIGNATURES["dpt_explore_weights"] = (_i32, [_c_void_p, _i32, _i32, _f64, _c_void_p, _c_void_p])
 SIGNATURES["dpt_explore_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i32, ctypes.POINTER(_i64)])
 SIGNATURES["dpt_explore_grad"] = (_i32, [_train_desc_p, _c_void_p, _c_void_p, ctypes.POINTER(ExploreArgs), _c_void_p])
+
+
+SITE_IMAGE_ENC = 1 << 20  # Philox site of the image encoder's dropout (DPT_SITE_IMAGE_ENC)
+
+
+class ImageDesc(ctypes.Structure):
+    """dpt_image_desc: the image front end of ImageTransformer (encoder, embed_transition, embed_ln)."""
+    _fields_ = [("image_size", _i32), ("rows", _i32), ("state_dim", _i32), ("action_dim", _i32), ("n_embd", _i32),
+                ("flags", _i32), ("dropout", ctypes.c_float), ("reserved", _i32), ("dropout_seed", ctypes.c_uint64)]
+
+
+_image_desc_p = ctypes.POINTER(ImageDesc)
+SIGNATURES["dpt_image_front_blob_numel"] = (_i32, [_image_desc_p, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_image_front_workspace_numel"] = (_i32, [_image_desc_p, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_image_front_forward"] = (_i32, [_image_desc_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                                _c_void_p])
+SIGNATURES["dpt_image_front_backward"] = (_i32, [_image_desc_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                                 _c_void_p, _c_void_p])
+SIGNATURES["dpt_train_forward_embeds"] = (_i32, [_train_desc_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_train_backward_embeds"] = (_i32, [_train_desc_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                                  _c_void_p, _c_void_p])

@@ -8,6 +8,10 @@ the reference's parameter shapes (nn.Linear weights are stored [out][in] by torc
 in the blob).  Everything runs on the device; the library owns no memory here (the workspace
 holding the forward's saved activations is a torch tensor kept on the autograd context).
 
+``ImageTransformerFunction`` is the autograd node of ``models.net.ImageTransformer.forward``: the HIP
+image front end (dpt_image_front_forward / _backward: conv encoder, embed_transition, embed_ln) chained
+into the trunk through dpt_train_forward_embeds / dpt_train_backward_embeds.
+
 ``Trainer`` is the fused training step that train.py runs (dpt_train_step: batch packing from a
 device-resident dataset, forward, summed cross-entropy, backward, AdamW on the packed blob) with
 the master weights, the optimizer state and the loss accumulator kept on the device.
@@ -184,6 +188,165 @@ class TransformerFunction(torch.autograd.Function):
         grads = [g if g.device == dv else g.to(dv) for g, dv in zip(_unpack(dblob, shapes, dtypes), devs)]
         ctx.ws = None  # the saved activations are not needed again
         return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+# ----------------------------------------------------------------------------- image-conditioned DPT
+IMAGE_SIZE = 25  # the only image size the front end is built for
+
+
+def image_desc(rows, state_dim, action_dim, n_embd, flags=0, dropout=0.0, seed=0, image_size=IMAGE_SIZE):
+    """dpt_image_desc of the image front end (encoder -> embed_transition -> embed_ln) over ``rows``
+    images; ``dropout`` / ``seed`` as in the step's dpt_train_desc (the encoder's nn.Dropout)."""
+    return _lib.ImageDesc(image_size, rows, state_dim, action_dim, n_embd, flags, dropout, 0, seed)
+
+
+def front_forward(d, blob, images, feats):
+    """embeds (rows, E) = embed_ln(embed_transition([encoder(images) | feats])) + the workspace the
+    backward needs.  images (rows, 3, 25, 25) normalised fp32, feats (rows, sd + A + 1)."""
+    _on_device(blob, images, feats)
+    if tuple(images.shape) != (d.rows, 3, d.image_size, d.image_size) or \
+            tuple(feats.shape) != (d.rows, d.state_dim + d.action_dim + 1):
+        raise ValueError(f"images {tuple(images.shape)} / feats {tuple(feats.shape)} do not match the description")
+    if blob.numel() != _numel("dpt_image_front_blob_numel", d):
+        raise ValueError("front parameter shapes do not match the description")
+    ws = torch.empty(_numel("dpt_image_front_workspace_numel", d), dtype=torch.float32, device=blob.device)
+    embeds = torch.empty((d.rows, d.n_embd), dtype=torch.float32, device=blob.device)
+    _lib.call("dpt_image_front_forward", ctypes.byref(d), _p(blob), _p(images), _p(feats), _p(ws), _p(embeds),
+              _stream())
+    return embeds, ws
+
+
+def front_backward(d, blob, images, feats, ws, dembeds):
+    """dL/d(front blob) (front blob order) from dL/dembeds (rows, E)."""
+    de = dembeds.to(torch.float32).contiguous()
+    _on_device(blob, images, feats, ws, de)
+    if tuple(de.shape) != (d.rows, d.n_embd):
+        raise ValueError(f"dembeds {tuple(de.shape)} do not match the description")
+    dblob = torch.empty(_numel("dpt_image_front_blob_numel", d), dtype=torch.float32, device=blob.device)
+    _lib.call("dpt_image_front_backward", ctypes.byref(d), _p(blob), _p(images), _p(feats), _p(ws), _p(de),
+              _p(dblob), _stream())
+    return dblob
+
+
+def forward_embeds(d, blob, embeds):
+    """``forward`` with the token embedding skipped (dpt_train_forward_embeds): embeds (batch, window, E)
+    enter as x0 = drop(embeds + wpe); the blob keeps its layout and its emb_w / emb_b region is not read."""
+    _on_device(blob, embeds)
+    if embeds.numel() != d.batch * d.window * d.n_embd:
+        raise ValueError(f"embeds {tuple(embeds.shape)} do not match the description")
+    ws = torch.empty(_numel("dpt_train_workspace_numel", d), dtype=torch.float32, device=blob.device)
+    preds = torch.empty((d.batch, d.window, d.action_dim), dtype=torch.float32, device=blob.device)
+    _lib.call("dpt_train_forward_embeds", ctypes.byref(d), _p(blob), _p(embeds), _p(ws), _p(preds), _stream())
+    return preds, ws
+
+
+def backward_embeds(d, blob, ws, dpreds):
+    """(dL/dblob with an exactly zero emb_w / emb_b region, dL/dembeds (batch, window, E))."""
+    dp = dpreds.to(torch.float32).contiguous()
+    _on_device(blob, ws, dp)
+    if dp.shape != (d.batch, d.window, d.action_dim):
+        raise ValueError(f"dpreds {tuple(dp.shape)} do not match the description")
+    dblob = torch.empty(_numel("dpt_train_blob_numel", d), dtype=torch.float32, device=blob.device)
+    dembeds = torch.empty((d.batch, d.window, d.n_embd), dtype=torch.float32, device=blob.device)
+    _lib.call("dpt_train_backward_embeds", ctypes.byref(d), _p(blob), _p(ws), _p(dp), _p(dblob), _p(dembeds),
+              _stream())
+    return dblob, dembeds
+
+
+def image_param_list(model):
+    """An ImageTransformer's parameters as the image function takes them: the front end in front-blob
+    order (dpt_hip.FRONT_KEYS), then the trunk in blob order without embed_transition."""
+    from . import FRONT_KEYS
+    named = dict(model.named_parameters())
+    return [named[k] for k in FRONT_KEYS] + param_list(model)[2:]
+
+
+N_FRONT = 10  # parameters of the front end (dpt_hip.FRONT_KEYS)
+
+
+def pack_image_params(params, emb_numel, dev):
+    """(front blob, trunk blob) of ``image_param_list``'s parameters; the trunk blob keeps the
+    dpt_train_desc layout with a zero emb_w / emb_b region of ``emb_numel`` floats (never read)."""
+    from . import FRONT_KEYS, pack_front
+    with torch.no_grad():
+        ps = [p.detach().to(device=dev, dtype=torch.float32) for p in params]
+        front = pack_front(dict(zip(FRONT_KEYS, ps[:N_FRONT])))
+        trunk = ps[N_FRONT:]
+        trunk[-2] = trunk[-2].t()  # pred_actions.weight: [out][in] -> [in][out]
+        tblob = torch.cat([torch.zeros(emb_numel, dtype=torch.float32, device=dev)] + [p.reshape(-1) for p in trunk])
+    return front, tblob
+
+
+def unpack_image_grads(dfront, dtrunk, emb_numel, shapes):
+    """Per-parameter gradients (``image_param_list`` order, shaped like the parameters) from the two
+    gradient blobs."""
+    out, off = [], 0
+    for i, sh in enumerate(shapes[:N_FRONT]):
+        n = int(torch.Size(sh).numel())
+        flat = dfront[off:off + n]
+        out.append(flat.view(sh[1], sh[0]).t() if i in (4, 6) else flat.view(sh))  # fc / embed_transition weights
+        off += n
+    if off != dfront.numel():
+        raise ValueError(f"front gradient blob {dfront.numel()} != parameters {off}")
+    off, n_all = emb_numel, len(shapes)
+    for i, sh in enumerate(shapes[N_FRONT:], N_FRONT):
+        n = int(torch.Size(sh).numel())
+        flat = dtrunk[off:off + n]
+        out.append(flat.view(sh[1], sh[0]).t() if i == n_all - 2 else flat.view(sh))
+        off += n
+    if off != dtrunk.numel():
+        raise ValueError(f"gradient blob {dtrunk.numel()} != parameters {off}")
+    return out
+
+
+class ImageTransformerFunction(torch.autograd.Function):
+    """preds (B, T, A) = ImageTransformer(images, feats) at every position: the HIP image front end
+    chained into the trunk (front forward -> dpt_train_forward_embeds) and, in ``backward``, the
+    trunk's backward handing dL/dembeds to the front end's.  ``dims`` as TransformerFunction's:
+    (n_layer, n_embd, state_dim, action_dim, n_positions, batch, window, flags, dropout p, seed);
+    ``params`` = ``image_param_list(model)``."""
+
+    @staticmethod
+    def forward(ctx, images, feats, dims, *params):
+        L, E, sd, A, npos, B, T = (int(v) for v in dims[:7])
+        flags = dims[7] if len(dims) > 7 else 0
+        p, seed = (float(dims[8]), int(dims[9])) if len(dims) > 9 else (0.0, 0)
+        need = any(ctx.needs_input_grad[3:]) and not flags & FORWARD_ONLY
+        last = bool(flags & LAST_ONLY) and p == 0.0
+        td = desc(L, E, sd, A, npos, B, T, flags=0 if need else FORWARD_ONLY | (LAST_ONLY if last else 0), dropout=p,
+                  seed=seed)
+        fd = image_desc(B * T, sd, A, E, flags=0 if need else FORWARD_ONLY, dropout=p, seed=seed)
+        dev = device()
+        emb_numel = (2 * sd + A + 1) * E + E
+        fblob, tblob = pack_image_params(params, emb_numel, dev)
+        if tblob.numel() != _numel("dpt_train_blob_numel", td):
+            raise ValueError("parameter shapes do not match the model description")
+        img = images.to(device=dev, dtype=torch.float32).reshape(B * T, 3, IMAGE_SIZE, IMAGE_SIZE).contiguous()
+        ft = feats.to(device=dev, dtype=torch.float32).reshape(B * T, sd + A + 1).contiguous()
+        embeds, fws = front_forward(fd, fblob, img, ft)
+        preds, tws = forward_embeds(td, tblob, embeds)
+        if need:
+            ctx.saved = (td, fd, fblob, tblob, img, ft, fws, tws, emb_numel)
+            ctx.params_meta = ([tuple(q.shape) for q in params], [q.dtype for q in params], [q.device for q in params])
+        ctx.forward_only = bool(flags & FORWARD_ONLY) and any(ctx.needs_input_grad[3:])
+        return preds
+
+    @staticmethod
+    def backward(ctx, dpreds):
+        if getattr(ctx, "forward_only", False):
+            raise RuntimeError("dpt_hip.train: this forward ran with FORWARD_ONLY (no activations saved) while "
+                               "parameters require grad; drop the FORWARD_ONLY flag to train through it")
+        if getattr(ctx, "saved", None) is None:
+            raise RuntimeError("dpt_hip.train: the saved activations were released by the first backward; "
+                               "a second backward through the same graph (retain_graph=True) is not supported")
+        td, fd, fblob, tblob, img, ft, fws, tws, emb_numel = ctx.saved
+        dtrunk, dembeds = backward_embeds(td, tblob, tws, dpreds)
+        dfront = front_backward(fd, fblob, img, ft, fws, dembeds.view(fd.rows, fd.n_embd))
+        shapes, dtypes, devs = ctx.params_meta
+        grads = unpack_image_grads(dfront, dtrunk, emb_numel, shapes)
+        grads = [g.to(device=dv, dtype=dt) for g, dt, dv in zip(grads, dtypes, devs)]
+        ctx.saved = None  # the saved activations are not needed again
+        return (None, None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
 
 
 DATA_KEYS = ("query_states", "context_states", "context_actions", "context_next_states", "context_rewards",

@@ -214,3 +214,72 @@ class Transformer(nn.Module):
         cr = x["context_rewards"]
         return dm.forward_window(query, cs, x["context_actions"], x["context_next_states"],
                                  cr.reshape(cr.shape[0], C), out_mode=0 if self.test else 1)
+
+
+class ImageTransformer(Transformer):
+    """Transformer class for image-based data (models/net.py:63-132): per token an image goes
+    through a small conv encoder, and [enc | state | action | reward] through ``embed_transition``
+    and ``embed_ln`` into the GPT-2 stack.  Same config dict (plus ``image_size``) and parameter
+    names as the reference, so its checkpoints load with a strict ``load_state_dict``.
+
+    ``image_encoder`` is a plain ``nn.Sequential`` holding the reference's layers (its indices name
+    the parameters); ``forward`` never calls it: the encoder, ``embed_transition`` and ``embed_ln``
+    run as the HIP image front end chained into the trunk's training kernels
+    (dpt_hip.train.ImageTransformerFunction), forward and backward.  Only ``image_size`` 25 (the
+    reference's, train.py:196) is built."""
+
+    def __init__(self, config):
+        super().__init__(config)
+        self.im_embd = 8
+        size = self.config["image_size"]
+        if size != 25:
+            raise NotImplementedError(f"image_size={size}: the image front end is built for 25 only")
+        size = (size - 3) // 2 + 1
+        size = (size - 3) // 1 + 1
+        # torch's default initialisation for the encoder, as in the reference
+        self.image_encoder = nn.Sequential(
+            nn.Conv2d(3, 16, kernel_size=3, stride=2),
+            nn.ReLU(),
+            nn.Conv2d(16, 16, kernel_size=3, stride=1),
+            nn.ReLU(),
+            nn.Dropout(self.dropout),
+            nn.Flatten(start_dim=1),
+            nn.Linear(int(16 * size * size), self.im_embd),
+            nn.ReLU(),
+        )
+        new_dim = self.im_embd + self.state_dim + self.action_dim + 1
+        self.embed_transition = nn.Linear(new_dim, self.n_embd)
+        self.embed_ln = nn.LayerNorm(self.n_embd)
+        with torch.no_grad():  # GPT-2's initialisation for the rest (_init_gpt2)
+            self.embed_transition.weight.normal_(0.0, 0.02)
+            self.embed_transition.bias.zero_()
+
+    def device_model(self):
+        raise NotImplementedError("ImageTransformer runs on the image front end and the training kernels "
+                                  "(dpt_hip.train.ImageTransformerFunction); it has no fused rollout model")
+
+    def forward(self, x):
+        """models/net.py:89-132: [query | context] images and [state | action | reward] features ->
+        encoder -> embed_transition -> embed_ln -> GPT-2 -> head; last position (test) or positions 1..
+        ``context_rewards`` may have 2 or 3 dims.  Inference (no grad, or no trainable parameter) runs
+        forward-only kernels; training-mode dropout draws its masks as ``Transformer.forward`` does."""
+        from dpt_hip import train as tr
+        dev = dpt_hip.device()
+        f32 = lambda k: x[k].to(dev, torch.float32)  # noqa: E731
+        query_images, context_images = f32("query_images")[:, None], f32("context_images")
+        B, C = query_images.shape[0], context_images.shape[1]
+        rewards = f32("context_rewards").reshape(B, C, 1)
+        images = torch.cat([query_images, context_images], dim=1)
+        states = torch.cat([f32("query_states")[:, None, :], f32("context_states")], dim=1)
+        actions = torch.cat([torch.zeros((B, 1, self.action_dim), device=dev), f32("context_actions")], dim=1)
+        rewards = torch.cat([torch.zeros((B, 1, 1), device=dev), rewards], dim=1)
+        feats = torch.cat([states, actions, rewards], dim=2)
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        p, seed = 0.0, 0
+        if self.training and self.dropout > 0:  # fresh masks per call (_dropout_seed)
+            p, seed = float(self.dropout), _dropout_seed()
+        flags = 0 if grad else tr.FORWARD_ONLY | (tr.LAST_ONLY if self.test and p == 0.0 else 0)
+        dims = (self.n_layer, self.n_embd, self.state_dim, self.action_dim, self.n_positions, B, 1 + C, flags, p,
+                seed)
+        preds = tr.ImageTransformerFunction.apply(images, feats, dims, *tr.image_param_list(self))
+        return preds[:, -1, :] if self.test else preds[:, 1:, :]

@@ -89,7 +89,7 @@ def main(argv=None):
         dataset_config.update({"rollin_type": "uniform"})
         data_name, model_name = build_darkroom_data_filename, build_darkroom_model_filename
     else:
-        raise NotImplementedError(f"{env} (miniworld is out of scope)")
+        raise NotImplementedError(f"{env} (miniworld trains with train_miniworld.py)")
     path_train = data_name(env, n_envs, dataset_config, mode=0)
     path_test = data_name(env, n_envs, dataset_config, mode=1)
     filename = model_name(env, model_config)

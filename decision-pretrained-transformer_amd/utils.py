@@ -75,6 +75,23 @@ def build_darkroom_model_filename(env, config):
     return _model_filename("darkroom", env, config)
 
 
+def build_miniworld_data_filename(env, env_id_start, env_id_end, config, mode):
+    """Mode 0: train, 1: test, 2: eval (utils.py:152-171): one file per range of env ids."""
+    name = f"{env}_start{env_id_start}_end{env_id_end}"
+    if mode != 2:
+        name += f"_hists{config['n_hists']}_samples{config['n_samples']}"
+    name += f"_H{config['horizon']}"
+    if mode == 2:
+        name += "_" + config["rollin_type"] + "_eval"
+    else:
+        name += _MODE_SUFFIX.get(mode, "")
+    return f"datasets/trajs_{name}.pkl"
+
+
+def build_miniworld_model_filename(env, config):
+    return env + _fields(config, _MODEL_HEAD) + _fields(config, [("_H", "horizon"), ("_seed", "seed")])
+
+
 def convert_to_tensor(x, store_gpu=True):
     """numpy/list -> float32 tensor, on the device by default (utils.py:193-197)."""
     t = torch.tensor(np.asarray(x)).float()

@@ -688,6 +688,55 @@ int dpt_explore_workspace_numel(const dpt_train_desc* desc_host, int32_t N, int3
 int dpt_explore_grad(const dpt_train_desc* desc_host, const float* explorer_blob, const float* exploiter_blob,
                      const dpt_explore_args* args_host, void* stream);
 
+/* ------------------------------------------------------------------ image-conditioned DPT (ImageTransformer)
+ * models/net.py:63-132: per token an image (3, 25, 25) goes through Conv2d(3,16,k3,s2) -> ReLU ->
+ * Conv2d(16,16,k3,s1) -> ReLU -> Dropout(p) -> flatten (c, y, x) -> Linear(1600, 8) -> ReLU; the token
+ * [enc(8) | state | action | reward] goes through embed_transition and embed_ln (eps 1e-5), and the
+ * result enters the GPT-2 trunk as its input embedding.
+ *
+ * The trunk with the token embedding skipped: dpt_train_forward_embeds / dpt_train_backward_embeds are
+ * dpt_train_forward / dpt_train_backward with x0 = drop_site0(embeds + wpe[t]) (embeds (batch, window,
+ * n_embd)), every flag and dropout included.  Blob and workspace keep the dpt_train_desc layout; the
+ * emb_w / emb_b region is not read and its gradient is written as exact zeros.  The backward writes
+ * dembeds (batch, window, n_embd) = dL/dx0 after the site-0 mask, position 0 included. */
+int dpt_train_forward_embeds(const dpt_train_desc* desc_host, const float* blob, const float* embeds,
+                             float* workspace, float* preds, void* stream);
+int dpt_train_backward_embeds(const dpt_train_desc* desc_host, const float* blob, float* workspace,
+                              const float* dpreds, float* dblob, float* dembeds, void* stream);
+
+/* The front end.  Front blob (floats, in this order):
+ *   conv1_w[16][3][3][3] conv1_b[16] conv2_w[16][16][3][3] conv2_b[16]   (torch's layout)
+ *   fc_w[1600][8] fc_b[8] emb_w[8 + sd + A + 1][E] emb_b[E]              (nn.Linear stored [in][out])
+ *   embln_g[E] embln_b[E]
+ * The encoder's dropout is Philox site DPT_SITE_IMAGE_ENC, element row 1600 + c 100 + y 10 + x, with the
+ * keep rule and scale of dpt_train_desc; the backward regenerates the mask from the desc.  Weight and
+ * bias gradients are reduced in a fixed order: repeated calls are bit-identical. */
+#define DPT_SITE_IMAGE_ENC 1048576 /* 1 << 20: clear of the trunk's sites 1 + 3 l .. 3 + 3 l */
+typedef struct dpt_image_desc {
+    int32_t image_size;           /* 25: the only size built; anything else is rejected before a launch */
+    int32_t rows;                 /* images = batch * window */
+    int32_t state_dim, action_dim, n_embd;
+    int32_t flags;                /* DPT_TRAIN_FORWARD_ONLY or 0 */
+    float dropout;                /* the encoder's nn.Dropout, same p as the trunk */
+    int32_t reserved;             /* 0 */
+    uint64_t dropout_seed;        /* the same seed as the step's dpt_train_desc */
+} dpt_image_desc;
+int dpt_image_front_blob_numel(const dpt_image_desc* desc_host, int64_t* numel_out_host);
+/* floats; with DPT_TRAIN_FORWARD_ONLY only the token rows, the pre-LayerNorm rows and their statistics */
+int dpt_image_front_workspace_numel(const dpt_image_desc* desc_host, int64_t* numel_out_host);
+/* images (rows, 3, 25, 25) normalised fp32; feats (rows, sd + A + 1) = [state | action | reward];
+ * embeds (rows, E) = embed_ln(embed_transition([enc | feats])).  Keeps in `workspace` what the backward
+ * needs (the dropped conv2 activations, the token rows, the pre-LayerNorm rows and statistics). */
+int dpt_image_front_forward(const dpt_image_desc* desc_host, const float* front_blob, const float* images,
+                            const float* feats, float* workspace, float* embeds, void* stream);
+/* dfront_blob (front blob layout) from dembeds (rows, E); pass the forward's desc, images, feats and
+ * workspace unchanged.  Host checks fail before any launch: null pointers, rows < 1, image_size != 25
+ * (DPT_EUNSUPPORTED), n_embd < 1, state_dim < 0, action_dim < 1, dropout outside [0, 1), reserved != 0,
+ * unknown flags, a workspace that is not 16-byte aligned, a backward on a DPT_TRAIN_FORWARD_ONLY desc. */
+int dpt_image_front_backward(const dpt_image_desc* desc_host, const float* front_blob, const float* images,
+                             const float* feats, float* workspace, const float* dembeds, float* dfront_blob,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
