@@ -26,6 +26,25 @@ typedef double doublex2 __attribute__((ext_vector_type(2)));
 void set_error(int code, const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);
 
+// host glue of the entry points: argument checks, the stream handle, 16-byte region sizes, launch errors
+#define DPT_REQUIRE(cond, ...)                     \
+    do {                                           \
+        if (!(cond)) {                             \
+            set_error(DPT_EINVAL, __VA_ARGS__);    \
+            return DPT_EINVAL;                     \
+        }                                          \
+    } while (0)
+
+inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+inline int64_t round4(int64_t n) { return (n + 3) & ~int64_t(3); }
+inline int launched(const char* what) { return check_hip(hipGetLastError(), what); }
+// the cross-entropy entry points and the steps built on them take at most kMaxA actions
+inline int check_action_dim(const char* who, int A) {
+    if (A <= kMaxA) return DPT_OK;
+    set_error(DPT_EUNSUPPORTED, "%s: action_dim=%d above %d", who, A, kMaxA);
+    return DPT_EUNSUPPORTED;
+}
+
 // ----------------------------------------------------------------------------- model view
 // Offsets (in floats) inside one transformer block of the packed blob, dpt_hip.h order.
 struct LayerOff {
@@ -366,6 +385,24 @@ struct GenEnvAct {
 int ia_check_shape(const dpt_train_desc* d, int32_t N, int32_t K, int32_t min_K, const char* who,
                    dpt_train_desc& run);
 int ia_accumulate(float* dst, const float* src, int64_t numel, void* stream);
+
+// The hard-target cross-entropy of one row of A fp32 logits, in fp64 per element with one rounding on
+// the store: returns lse(x) - x[tg] and, with dx, stores dx = sw (softmax(x) - onehot(tg)).  tg lies
+// in [0, A): the callers store their explicit zeros (no class, weight 0, rows the loss skips) themselves.
+__device__ inline double ce_hard_row(const float* x, int A, int64_t tg, double sw, float* dx) {
+    float mf = x[0];
+    for (int k = 1; k < A; ++k) mf = fmaxf(mf, x[k]);
+    const double m = (double)mf;
+    double s = 0.0;
+    for (int k = 0; k < A; ++k) s += exp((double)x[k] - m);
+    const double lse = m + log(s);
+    if (dx)
+        for (int k = 0; k < A; ++k) dx[k] = (float)(sw * (exp((double)x[k] - lse) - (k == tg ? 1.0 : 0.0)));
+    return lse - (double)x[tg];
+}
+// *acc += scale * sum_i w_i values[i], w = weights or 1 (a weight of 0 adds nothing, whatever the value):
+// one workgroup, thread-strided sums, then an LDS tree -- a fixed order (defined in dpt_trainstep.hip)
+void ce_finish(const double* values, const double* weights, int64_t n, double scale, double* acc, hipStream_t st);
 
 struct L0Off {
     static constexpr int G = 0;                // Wq Wk^T: u = xn G + g0 = Wk q

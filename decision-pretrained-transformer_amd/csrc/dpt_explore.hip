@@ -17,18 +17,6 @@ namespace dpt {
 
 constexpr int kExThreads = 256;
 
-#define EX_REQUIRE(cond, ...)                      \
-    do {                                           \
-        if (!(cond)) {                             \
-            set_error(DPT_EINVAL, __VA_ARGS__);    \
-            return DPT_EINVAL;                     \
-        }                                          \
-    } while (0)
-
-static hipStream_t ex_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static int64_t ex_round4(int64_t n) { return (n + 3) & ~int64_t(3); }
-static int launched_ex(const char* what) { return check_hip(hipGetLastError(), what); }
-
 // ----------------------------------------------------------------------------- every-position cross-entropy
 // One thread per row (b, t) of preds.  The target is tseq[b] or trow[row]; w = weights[row] or 1.
 // rowloss[row] = lse(x) - x[target] (unweighted) and dpreds = scale w (softmax(x) - onehot(target)),
@@ -49,42 +37,12 @@ __global__ __launch_bounds__(kExThreads) void ex_ce_rows_kernel(const float* __r
             for (int k = 0; k < A; ++k) dx[k] = 0.f;
         return;
     }
-    const float* x = preds + row * A;
-    float mf = x[0];
-    for (int k = 1; k < A; ++k) mf = fmaxf(mf, x[k]);
-    const double m = (double)mf;
-    double s = 0.0;
-    for (int k = 0; k < A; ++k) s += exp((double)x[k] - m);
-    const double lse = m + log(s);
-    rowloss[row] = lse - (double)x[tg];
-    if (!dx) return;
-    const double w = weights ? weights[row] : 1.0;
-    if (w == 0.0) {
+    const double w = dx && weights ? weights[row] : 1.0;
+    if (dx && w == 0.0) {  // the row loss alone
         for (int k = 0; k < A; ++k) dx[k] = 0.f;
-        return;
+        dx = nullptr;
     }
-    const double sw = scale * w;
-    for (int k = 0; k < A; ++k) dx[k] = (float)(sw * (exp((double)x[k] - lse) - (k == tg ? 1.0 : 0.0)));
-}
-
-// *acc += scale * sum_rows w[row] rowloss[row], one workgroup: thread-strided sums, then an LDS tree
-// (a row of weight 0 adds nothing, whatever its loss)
-__global__ __launch_bounds__(kExThreads) void ex_ce_finish_kernel(const double* __restrict__ rowloss,
-                                                                  const double* __restrict__ weights, int64_t rows,
-                                                                  double scale, double* __restrict__ acc) {
-    __shared__ double red[kExThreads];
-    double s = 0.0;
-    for (int64_t r = threadIdx.x; r < rows; r += kExThreads) {
-        const double w = weights ? weights[r] : 1.0;
-        if (w != 0.0) s += w * rowloss[r];
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = kExThreads / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *acc += scale * red[0];
+    rowloss[row] = ce_hard_row(preds + row * A, A, tg, scale * w, dx);
 }
 
 // ----------------------------------------------------------------------------- advantage weights
@@ -117,16 +75,16 @@ static int ex_ws(const dpt_train_desc* run, ExWs& w, int64_t* nblob_out) {
     const int64_t N = run->batch, K = run->window, A = run->action_dim, F = A + 3;
     if (int rc = dpt_rollout_bandit_generic_workspace_numel(run, (int32_t)N, (int32_t)(K - 1), &nroll)) return rc;
     w.train = 0;
-    w.tokens = ex_round4(nws);
-    w.preds = w.tokens + ex_round4(N * K * F);
-    w.dpreds = w.preds + ex_round4(N * K * A);
-    w.grad = w.dpreds + ex_round4(N * K * A);
-    w.rowloss = w.grad + ex_round4(nblob);               // (N, K) doubles
-    w.weights = w.rowloss + ex_round4(2 * N * K);        // (N, K) doubles
-    w.trow = w.weights + ex_round4(2 * N * K);           // (N, K) int32: the explorer's per-row targets
-    w.arm_value = w.trow + ex_round4(N * K);             // (N, K - 1) doubles, the rollout's arm_value_out
-    w.rollout = w.arm_value + ex_round4(2 * N * (K - 1));
-    w.total = w.rollout + ex_round4(nroll);
+    w.tokens = round4(nws);
+    w.preds = w.tokens + round4(N * K * F);
+    w.dpreds = w.preds + round4(N * K * A);
+    w.grad = w.dpreds + round4(N * K * A);
+    w.rowloss = w.grad + round4(nblob);               // (N, K) doubles
+    w.weights = w.rowloss + round4(2 * N * K);        // (N, K) doubles
+    w.trow = w.weights + round4(2 * N * K);           // (N, K) int32: the explorer's per-row targets
+    w.arm_value = w.trow + round4(N * K);             // (N, K - 1) doubles, the rollout's arm_value_out
+    w.rollout = w.arm_value + round4(2 * N * (K - 1));
+    w.total = w.rollout + round4(nroll);
     if (nblob_out) *nblob_out = nblob;
     return DPT_OK;
 }
@@ -140,10 +98,10 @@ static int ex_weights(const double* rowloss, int32_t B, int32_t T, double inv_be
                       const int32_t* actions, int32_t* trow, void* stream) {
     const int64_t rows = (int64_t)B * T;
     const int64_t blocks = (rows + kExThreads - 1) / kExThreads;
-    EX_REQUIRE(blocks < (1ll << 31), "explore weights: %lld rows", (long long)rows);
-    hipLaunchKernelGGL(ex_weights_kernel, dim3((unsigned)blocks), dim3(kExThreads), 0, ex_stream(stream), rowloss, B,
+    DPT_REQUIRE(blocks < (1ll << 31), "explore weights: %lld rows", (long long)rows);
+    hipLaunchKernelGGL(ex_weights_kernel, dim3((unsigned)blocks), dim3(kExThreads), 0, as_stream(stream), rowloss, B,
                        T, inv_beta, weights, actions, trow);
-    return launched_ex("ex_weights");
+    return launched("ex_weights");
 }
 
 }  // namespace dpt
@@ -155,34 +113,30 @@ extern "C" {
 int dpt_train_ce_rows(const float* preds, const int64_t* targets_seq, const int32_t* targets_row,
                       const double* weights, int32_t batch, int32_t window, int32_t A, double scale,
                       double* rowloss, float* dpreds, double* loss_acc, void* stream) {
-    EX_REQUIRE(preds && rowloss && loss_acc, "train ce rows: null pointer");
-    EX_REQUIRE((targets_seq != nullptr) != (targets_row != nullptr),
-               "train ce rows: exactly one of targets_seq / targets_row must be given");
-    EX_REQUIRE(batch >= 1 && window >= 1 && A >= 1, "train ce rows: batch=%d window=%d A=%d", batch, window, A);
-    if (A > kMaxA) {
-        set_error(DPT_EUNSUPPORTED, "train ce rows: action_dim=%d above %d", A, kMaxA);
-        return DPT_EUNSUPPORTED;
-    }
+    DPT_REQUIRE(preds && rowloss && loss_acc, "train ce rows: null pointer");
+    DPT_REQUIRE((targets_seq != nullptr) != (targets_row != nullptr),
+                "train ce rows: exactly one of targets_seq / targets_row must be given");
+    DPT_REQUIRE(batch >= 1 && window >= 1 && A >= 1, "train ce rows: batch=%d window=%d A=%d", batch, window, A);
+    if (int rc = check_action_dim("train ce rows", A)) return rc;
     const int64_t rows = (int64_t)batch * window;
     const int64_t blocks = (rows + kExThreads - 1) / kExThreads;
-    EX_REQUIRE(blocks < (1ll << 31), "train ce rows: %lld rows", (long long)rows);
-    hipLaunchKernelGGL(ex_ce_rows_kernel, dim3((unsigned)blocks), dim3(kExThreads), 0, ex_stream(stream), preds,
+    DPT_REQUIRE(blocks < (1ll << 31), "train ce rows: %lld rows", (long long)rows);
+    hipLaunchKernelGGL(ex_ce_rows_kernel, dim3((unsigned)blocks), dim3(kExThreads), 0, as_stream(stream), preds,
                        targets_seq, targets_row, weights, batch, window, A, scale, rowloss, dpreds);
-    hipLaunchKernelGGL(ex_ce_finish_kernel, dim3(1), dim3(kExThreads), 0, ex_stream(stream), rowloss, weights, rows,
-                       scale, loss_acc);
-    return launched_ex("ex_ce_rows");
+    ce_finish(rowloss, weights, rows, scale, loss_acc, as_stream(stream));
+    return launched("ex_ce_rows");
 }
 
 int dpt_explore_weights(const double* rowloss, int32_t batch, int32_t window, double inv_beta, double* weights,
                         void* stream) {
-    EX_REQUIRE(rowloss && weights, "explore weights: null pointer");
-    EX_REQUIRE(batch >= 1 && window >= 1, "explore weights: batch=%d window=%d", batch, window);
-    EX_REQUIRE(std::isfinite(inv_beta), "explore weights: inv_beta=%g", inv_beta);
+    DPT_REQUIRE(rowloss && weights, "explore weights: null pointer");
+    DPT_REQUIRE(batch >= 1 && window >= 1, "explore weights: batch=%d window=%d", batch, window);
+    DPT_REQUIRE(std::isfinite(inv_beta), "explore weights: inv_beta=%g", inv_beta);
     return ex_weights(rowloss, batch, window, inv_beta, weights, nullptr, nullptr, stream);
 }
 
 int dpt_explore_workspace_numel(const dpt_train_desc* d, int32_t N, int32_t K, int64_t* numel) {
-    EX_REQUIRE(numel != nullptr, "explore workspace: null numel");
+    DPT_REQUIRE(numel != nullptr, "explore workspace: null numel");
     dpt_train_desc run;
     if (int rc = ex_check_shape(d, N, K, run)) return rc;
     ExWs w;
@@ -193,23 +147,23 @@ int dpt_explore_workspace_numel(const dpt_train_desc* d, int32_t N, int32_t K, i
 
 int dpt_explore_grad(const dpt_train_desc* d, const float* explorer_blob, const float* exploiter_blob,
                      const dpt_explore_args* a, void* stream) {
-    EX_REQUIRE(d && explorer_blob && exploiter_blob && a, "explore grad: null desc / blob / args");
-    EX_REQUIRE(explorer_blob != exploiter_blob, "explore grad: the explorer and the exploiter share one blob");
-    EX_REQUIRE(a->means && a->targets && a->workspace && a->dblob_explorer && a->dblob_exploiter &&
-                   a->loss_explorer && a->loss_exploiter,
-               "explore grad: null pointer");
-    EX_REQUIRE(a->dblob_explorer != a->dblob_exploiter, "explore grad: the two gradient blobs are one buffer");
-    EX_REQUIRE(a->loss_explorer != a->loss_exploiter, "explore grad: the two loss accumulators are one buffer");
-    EX_REQUIRE(a->actions_out && a->rewards_out && a->env_actions_out,
-               "explore grad: null actions_out / env_actions_out / rewards_out");
+    DPT_REQUIRE(d && explorer_blob && exploiter_blob && a, "explore grad: null desc / blob / args");
+    DPT_REQUIRE(explorer_blob != exploiter_blob, "explore grad: the explorer and the exploiter share one blob");
+    DPT_REQUIRE(a->means && a->targets && a->workspace && a->dblob_explorer && a->dblob_exploiter &&
+                    a->loss_explorer && a->loss_exploiter,
+                "explore grad: null pointer");
+    DPT_REQUIRE(a->dblob_explorer != a->dblob_exploiter, "explore grad: the two gradient blobs are one buffer");
+    DPT_REQUIRE(a->loss_explorer != a->loss_exploiter, "explore grad: the two loss accumulators are one buffer");
+    DPT_REQUIRE(a->actions_out && a->rewards_out && a->env_actions_out,
+                "explore grad: null actions_out / env_actions_out / rewards_out");
     dpt_train_desc run;
     if (int rc = ex_check_shape(d, a->N, a->K, run)) return rc;
-    EX_REQUIRE(std::isfinite(a->beta) && a->beta > 0.0, "explore grad: beta=%g must be finite and > 0", a->beta);
+    DPT_REQUIRE(std::isfinite(a->beta) && a->beta > 0.0, "explore grad: beta=%g must be finite and > 0", a->beta);
     const int base = a->type & ~DPT_BANDIT_F32;
-    EX_REQUIRE(base == DPT_BANDIT_GAUSSIAN || base == DPT_BANDIT_BERNOULLI, "explore grad: bandit type %d", a->type);
-    EX_REQUIRE((a->flags & ~DPT_EXPLORE_ACCUMULATE) == 0, "explore grad: unknown flags 0x%x", a->flags);
+    DPT_REQUIRE(base == DPT_BANDIT_GAUSSIAN || base == DPT_BANDIT_BERNOULLI, "explore grad: bandit type %d", a->type);
+    DPT_REQUIRE((a->flags & ~DPT_EXPLORE_ACCUMULATE) == 0, "explore grad: unknown flags 0x%x", a->flags);
     const bool accumulate = (a->flags & DPT_EXPLORE_ACCUMULATE) != 0;
-    EX_REQUIRE((reinterpret_cast<uintptr_t>(a->workspace) & 15) == 0, "explore grad: workspace not 16-byte aligned");
+    DPT_REQUIRE((reinterpret_cast<uintptr_t>(a->workspace) & 15) == 0, "explore grad: workspace not 16-byte aligned");
     ExWs w;
     int64_t nblob = 0;
     if (int rc = ex_ws(&run, w, &nblob)) return rc;

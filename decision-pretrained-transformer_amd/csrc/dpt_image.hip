@@ -41,18 +41,6 @@ constexpr int kA1S = 148;
 constexpr int kDzW = 14, kDzS = kDzW * kDzW;  // dz2 with a zero border of 2: the data gradient reads (y - ky, x - kx)
 constexpr int kConvPart = 432 + 16 + 2304 + 16;  // one backward partial: conv1_w, conv1_b, conv2_w, conv2_b (blob order)
 
-#define IM_REQUIRE(cond, ...)                      \
-    do {                                           \
-        if (!(cond)) {                             \
-            set_error(DPT_EINVAL, __VA_ARGS__);    \
-            return DPT_EINVAL;                     \
-        }                                          \
-    } while (0)
-
-static hipStream_t im_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static int64_t im_round4(int64_t n) { return (n + 3) & ~int64_t(3); }
-static int launched_im(const char* what) { return check_hip(hipGetLastError(), what); }
-
 // front blob offsets (dpt_hip.h order); F = 8 + sd + A + 1
 struct ImgBlob {
     int64_t c1w, c1b, c2w, c2b, fcw, fcb, embw, embb, lng, lnb, total;
@@ -87,22 +75,22 @@ struct ImgWs {
         ImgWs w;
         const int64_t R = d.rows, E = d.E, F = d.F;
         int64_t p = 0;
-        w.tok = p; p += im_round4(R * F);   // [enc | feats], enc after its ReLU
-        w.h = p; p += im_round4(R * E);     // embed_transition's output (embed_ln's input)
-        w.st = p; p += im_round4(R * 2);    // embed_ln's (mean, rstd)
+        w.tok = p; p += round4(R * F);   // [enc | feats], enc after its ReLU
+        w.h = p; p += round4(R * E);     // embed_transition's output (embed_ln's input)
+        w.st = p; p += round4(R * 2);    // embed_ln's (mean, rstd)
         if (d.fwd_only) {
             w.a2 = w.dh = w.dtok = w.de = w.part = w.total = p;
             return w;
         }
         w.a2 = p; p += R * kFlat;           // conv2 activations after ReLU and dropout
-        w.dh = p; p += im_round4(R * E);
-        w.dtok = p; p += im_round4(R * F);
+        w.dh = p; p += round4(R * E);
+        w.dtok = p; p += round4(R * F);
         w.de = p; p += R * kEnc;            // dL/d(fc pre-activation)
         const int64_t nch = rows_chunks(R);
         int64_t part = std::max<int64_t>(nch * (F + 1) * E, nch * 2 * E);
         part = std::max<int64_t>(part, nch * (kFlat + 1) * kEnc);
         part = std::max<int64_t>(part, bwd_groups(d.rows) * kConvPart);
-        w.part = p; p += im_round4(part);
+        w.part = p; p += round4(part);
         w.total = p;
         return w;
     }
@@ -360,18 +348,18 @@ __global__ __launch_bounds__(kImgThreads) void img_enc_bwd(const float* __restri
 
 // ------------------------------------------------------------------------------ host side
 static int img_dims(const dpt_image_desc* d, ImgDims& o) {
-    IM_REQUIRE(d != nullptr, "image front: null desc");
+    DPT_REQUIRE(d != nullptr, "image front: null desc");
     if (d->image_size != kImgSize) {
         set_error(DPT_EUNSUPPORTED, "image front: image_size=%d (only %d is built)", d->image_size, kImgSize);
         return DPT_EUNSUPPORTED;
     }
-    IM_REQUIRE(d->rows >= 1 && d->rows <= (1 << 26), "image front: rows=%d", d->rows);
-    IM_REQUIRE(d->n_embd >= 1 && d->n_embd <= 1024, "image front: n_embd=%d", d->n_embd);
-    IM_REQUIRE(d->state_dim >= 0 && d->state_dim <= 4096, "image front: state_dim=%d", d->state_dim);
-    IM_REQUIRE(d->action_dim >= 1 && d->action_dim <= 4096, "image front: action_dim=%d", d->action_dim);
-    IM_REQUIRE(d->dropout >= 0.0f && d->dropout < 1.0f, "image front: dropout %g outside [0, 1)", (double)d->dropout);
-    IM_REQUIRE(d->reserved == 0, "image front: reserved=%d must be 0", d->reserved);
-    IM_REQUIRE((d->flags & ~DPT_TRAIN_FORWARD_ONLY) == 0, "image front: unknown flags 0x%x", d->flags);
+    DPT_REQUIRE(d->rows >= 1 && d->rows <= (1 << 26), "image front: rows=%d", d->rows);
+    DPT_REQUIRE(d->n_embd >= 1 && d->n_embd <= 1024, "image front: n_embd=%d", d->n_embd);
+    DPT_REQUIRE(d->state_dim >= 0 && d->state_dim <= 4096, "image front: state_dim=%d", d->state_dim);
+    DPT_REQUIRE(d->action_dim >= 1 && d->action_dim <= 4096, "image front: action_dim=%d", d->action_dim);
+    DPT_REQUIRE(d->dropout >= 0.0f && d->dropout < 1.0f, "image front: dropout %g outside [0, 1)", (double)d->dropout);
+    DPT_REQUIRE(d->reserved == 0, "image front: reserved=%d must be 0", d->reserved);
+    DPT_REQUIRE((d->flags & ~DPT_TRAIN_FORWARD_ONLY) == 0, "image front: unknown flags 0x%x", d->flags);
     o.rows = d->rows;
     o.G = d->state_dim + d->action_dim + 1;
     o.F = kEnc + o.G;
@@ -394,7 +382,7 @@ extern "C" {
 int dpt_image_front_blob_numel(const dpt_image_desc* d, int64_t* numel) {
     ImgDims t;
     if (int rc = img_dims(d, t)) return rc;
-    IM_REQUIRE(numel != nullptr, "image front: null numel");
+    DPT_REQUIRE(numel != nullptr, "image front: null numel");
     *numel = ImgBlob::make(t.F, t.E).total;
     return DPT_OK;
 }
@@ -402,7 +390,7 @@ int dpt_image_front_blob_numel(const dpt_image_desc* d, int64_t* numel) {
 int dpt_image_front_workspace_numel(const dpt_image_desc* d, int64_t* numel) {
     ImgDims t;
     if (int rc = img_dims(d, t)) return rc;
-    IM_REQUIRE(numel != nullptr, "image front: null numel");
+    DPT_REQUIRE(numel != nullptr, "image front: null numel");
     *numel = ImgWs::make(t).total;
     return DPT_OK;
 }
@@ -411,16 +399,16 @@ int dpt_image_front_forward(const dpt_image_desc* d, const float* blob, const fl
                             float* ws, float* embeds, void* stream) {
     ImgDims t;
     if (int rc = img_dims(d, t)) return rc;
-    IM_REQUIRE(blob && images && feats && ws && embeds, "image front forward: null pointer");
-    IM_REQUIRE(aligned16(ws), "image front forward: workspace not 16-byte aligned");
-    IM_REQUIRE(aligned16(blob), "image front forward: front blob not 16-byte aligned");
+    DPT_REQUIRE(blob && images && feats && ws && embeds, "image front forward: null pointer");
+    DPT_REQUIRE(aligned16(ws), "image front forward: workspace not 16-byte aligned");
+    DPT_REQUIRE(aligned16(blob), "image front forward: front blob not 16-byte aligned");
     const ImgBlob B = ImgBlob::make(t.F, t.E);
     const ImgWs W = ImgWs::make(t);
-    hipStream_t st = im_stream(stream);
+    hipStream_t st = as_stream(stream);
     const unsigned groups = (unsigned)(((int64_t)t.rows + kImgTileF - 1) / kImgTileF);
     hipLaunchKernelGGL(img_enc_fwd, dim3(groups), dim3(kImgThreads), 0, st, blob, images, feats, t,
                        t.fwd_only ? (float*)nullptr : ws + W.a2, ws + W.tok);
-    if (int rc = launched_im("img_enc_fwd")) return rc;
+    if (int rc = launched("img_enc_fwd")) return rc;
     if (int rc = rows_linear(ws + W.tok, blob + B.embw, blob + B.embb, t.rows, t.F, t.E, ws + W.h, st)) return rc;
     return rows_layernorm(ws + W.h, blob + B.lng, blob + B.lnb, t.rows, t.E, embeds, ws + W.st, st);
 }
@@ -429,13 +417,13 @@ int dpt_image_front_backward(const dpt_image_desc* d, const float* blob, const f
                              float* ws, const float* dembeds, float* dblob, void* stream) {
     ImgDims t;
     if (int rc = img_dims(d, t)) return rc;
-    IM_REQUIRE(blob && images && feats && ws && dembeds && dblob, "image front backward: null pointer");
-    IM_REQUIRE(!t.fwd_only, "image front backward: the description is forward-only (DPT_TRAIN_FORWARD_ONLY)");
-    IM_REQUIRE(aligned16(ws), "image front backward: workspace not 16-byte aligned");
-    IM_REQUIRE(aligned16(blob), "image front backward: front blob not 16-byte aligned");
+    DPT_REQUIRE(blob && images && feats && ws && dembeds && dblob, "image front backward: null pointer");
+    DPT_REQUIRE(!t.fwd_only, "image front backward: the description is forward-only (DPT_TRAIN_FORWARD_ONLY)");
+    DPT_REQUIRE(aligned16(ws), "image front backward: workspace not 16-byte aligned");
+    DPT_REQUIRE(aligned16(blob), "image front backward: front blob not 16-byte aligned");
     const ImgBlob B = ImgBlob::make(t.F, t.E);
     const ImgWs W = ImgWs::make(t);
-    hipStream_t st = im_stream(stream);
+    hipStream_t st = as_stream(stream);
     const int R = t.rows, E = t.E, F = t.F;
     float* part = ws + W.part;
     // embed_ln, then embed_transition
@@ -447,13 +435,13 @@ int dpt_image_front_backward(const dpt_image_desc* d, const float* blob, const f
     const int64_t ne = (int64_t)R * kEnc;
     hipLaunchKernelGGL(img_enc_relu_bwd, dim3((unsigned)((ne + kImgThreads - 1) / kImgThreads)), dim3(kImgThreads), 0, st,
                        ws + W.tok, ws + W.dtok, R, F, ws + W.de);
-    if (int rc = launched_im("img_enc_relu_bwd")) return rc;
+    if (int rc = launched("img_enc_relu_bwd")) return rc;
     if (int rc = rows_wgrad(ws + W.a2, ws + W.de, R, kFlat, kEnc, part, dblob + B.fcw, dblob + B.fcb, st)) return rc;
     // the convolutions: one partial per workgroup, then the fixed-order sum.  The 2768 floats of a partial
     // are the blob's first four arrays in order, reduced as a (172 + 1) x 16 product: conv2_b is its bias row
     const int groups = (int)ImgWs::bwd_groups(R);
     hipLaunchKernelGGL(img_enc_bwd, dim3(groups), dim3(kImgThreads), 0, st, blob, images, ws + W.a2, ws + W.de, t, part);
-    if (int rc = launched_im("img_enc_bwd")) return rc;
+    if (int rc = launched("img_enc_bwd")) return rc;
     static_assert(kConvPart == 173 * 16, "conv partial = 173 rows of 16");
     return rows_reduce_parts(part, groups, 172, 16, dblob + B.c1w, dblob + B.c2b, st);
 }

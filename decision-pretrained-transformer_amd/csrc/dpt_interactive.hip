@@ -15,18 +15,6 @@ namespace dpt {
 
 constexpr int kIaThreads = 256;
 
-#define IA_REQUIRE(cond, ...)                      \
-    do {                                           \
-        if (!(cond)) {                             \
-            set_error(DPT_EINVAL, __VA_ARGS__);    \
-            return DPT_EINVAL;                     \
-        }                                          \
-    } while (0)
-
-static hipStream_t ia_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static int64_t ia_round4(int64_t n) { return (n + 3) & ~int64_t(3); }
-static int launched_ia(const char* what) { return check_hip(hipGetLastError(), what); }
-
 // ----------------------------------------------------------------------------- pack
 // One thread per output float.  tokens (N, Hc + 1, A + 3): row 0 = [1, 0_A, 0, 0] (the query state
 // of a bandit is 1), row 1 + j = [1, onehot(a_j), 1, float(r_j)] (models/net.py:42-54 with state 1).
@@ -76,31 +64,7 @@ __global__ __launch_bounds__(kIaThreads) void ia_ce_last_kernel(const float* __r
             for (int k = 0; k < A; ++k) dx[k] = 0.f;
         return;
     }
-    const float* x = preds + row * A;
-    float mf = x[0];
-    for (int k = 1; k < A; ++k) mf = fmaxf(mf, x[k]);
-    const double m = (double)mf;
-    double s = 0.0;
-    for (int k = 0; k < A; ++k) s += exp((double)x[k] - m);
-    const double lse = m + log(s);
-    partial[b] = lse - (double)x[tg];
-    if (dx)
-        for (int k = 0; k < A; ++k) dx[k] = (float)(scale * (exp((double)x[k] - lse) - (k == tg ? 1.0 : 0.0)));
-}
-
-// *acc += scale * sum_b partial[b], one workgroup: thread-strided sums, then an LDS tree
-__global__ __launch_bounds__(kIaThreads) void ia_ce_finish_kernel(const double* __restrict__ partial, int B,
-                                                                  double scale, double* __restrict__ acc) {
-    __shared__ double red[kIaThreads];
-    double s = 0.0;
-    for (int b = threadIdx.x; b < B; b += kIaThreads) s += partial[b];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = kIaThreads / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *acc += scale * red[0];
+    partial[b] = ce_hard_row(preds + row * A, A, tg, scale, dx);
 }
 
 // dst += src, element by element (each element has one writer: the order is fixed)
@@ -124,14 +88,14 @@ static int ia_ws(const dpt_train_desc* run, IaWs& w, int64_t* nblob_out) {
     if (K > 1)
         if (int rc = dpt_rollout_bandit_generic_workspace_numel(run, (int32_t)N, (int32_t)(K - 1), &nroll)) return rc;
     w.train = 0;
-    w.tokens = ia_round4(nws);
-    w.preds = w.tokens + ia_round4(N * K * F);
-    w.dpreds = w.preds + ia_round4(N * K * A);
-    w.grad = w.dpreds + ia_round4(N * K * A);
-    w.partial = w.grad + ia_round4(nblob);              // N doubles
-    w.arm_value = w.partial + ia_round4(2 * N);         // (N, K - 1) doubles, the rollout's arm_value_out
-    w.rollout = w.arm_value + ia_round4(2 * N * (K - 1));
-    w.total = w.rollout + ia_round4(nroll);
+    w.tokens = round4(nws);
+    w.preds = w.tokens + round4(N * K * F);
+    w.dpreds = w.preds + round4(N * K * A);
+    w.grad = w.dpreds + round4(N * K * A);
+    w.partial = w.grad + round4(nblob);              // N doubles
+    w.arm_value = w.partial + round4(2 * N);         // (N, K - 1) doubles, the rollout's arm_value_out
+    w.rollout = w.arm_value + round4(2 * N * (K - 1));
+    w.total = w.rollout + round4(nroll);
     if (nblob_out) *nblob_out = nblob;
     return DPT_OK;
 }
@@ -140,18 +104,15 @@ static int ia_ws(const dpt_train_desc* run, IaWs& w, int64_t* nblob_out) {
 // "interactive", min_K 1) and the explorer/exploiter (dpt_explore.hip) training steps; fills `run`
 int ia_check_shape(const dpt_train_desc* d, int32_t N, int32_t K, int32_t min_K, const char* who,
                    dpt_train_desc& run) {
-    IA_REQUIRE(d != nullptr, "%s: null desc", who);
-    IA_REQUIRE(N >= 1, "%s: N=%d", who, N);
-    IA_REQUIRE(K >= min_K, "%s: K=%d (at least %d)", who, K, min_K);
-    IA_REQUIRE(K <= d->n_positions, "%s: K=%d exceeds n_positions=%d", who, K, d->n_positions);
-    IA_REQUIRE((int64_t)N * K <= (1ll << 26), "%s: N * K = %lld rows (use smaller chunks)", who, (long long)N * K);
-    IA_REQUIRE(d->state_dim == 1, "%s: state_dim=%d (bandits have state_dim 1)", who, d->state_dim);
-    if (d->action_dim > kMaxA) {
-        set_error(DPT_EUNSUPPORTED, "%s: action_dim=%d above %d", who, d->action_dim, kMaxA);
-        return DPT_EUNSUPPORTED;
-    }
-    IA_REQUIRE(d->dropout == 0.0f, "%s: dropout=%g must be 0 (the cached decode has no dropout masks)", who,
-               (double)d->dropout);
+    DPT_REQUIRE(d != nullptr, "%s: null desc", who);
+    DPT_REQUIRE(N >= 1, "%s: N=%d", who, N);
+    DPT_REQUIRE(K >= min_K, "%s: K=%d (at least %d)", who, K, min_K);
+    DPT_REQUIRE(K <= d->n_positions, "%s: K=%d exceeds n_positions=%d", who, K, d->n_positions);
+    DPT_REQUIRE((int64_t)N * K <= (1ll << 26), "%s: N * K = %lld rows (use smaller chunks)", who, (long long)N * K);
+    DPT_REQUIRE(d->state_dim == 1, "%s: state_dim=%d (bandits have state_dim 1)", who, d->state_dim);
+    if (int rc = check_action_dim(who, d->action_dim)) return rc;
+    DPT_REQUIRE(d->dropout == 0.0f, "%s: dropout=%g must be 0 (the cached decode has no dropout masks)", who,
+                (double)d->dropout);
     run = *d;
     run.batch = N;
     run.window = K;
@@ -162,9 +123,9 @@ int ia_check_shape(const dpt_train_desc* d, int32_t N, int32_t K, int32_t min_K,
 // dst += src over `numel` floats, one launch on `stream`
 int ia_accumulate(float* dst, const float* src, int64_t numel, void* stream) {
     const int64_t blocks = (numel + kIaThreads - 1) / kIaThreads;
-    hipLaunchKernelGGL(ia_accumulate_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, ia_stream(stream), dst, src,
+    hipLaunchKernelGGL(ia_accumulate_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, as_stream(stream), dst, src,
                        numel);
-    return launched_ia("ia_accumulate");
+    return launched("ia_accumulate");
 }
 
 }  // namespace dpt
@@ -175,36 +136,32 @@ extern "C" {
 
 int dpt_interactive_pack(const int32_t* actions, const double* rewards, int32_t N, int32_t Hc, int32_t A,
                          float* tokens, void* stream) {
-    IA_REQUIRE(tokens && (Hc == 0 || (actions && rewards)), "interactive pack: null pointer");
-    IA_REQUIRE(N >= 1 && Hc >= 0 && A >= 1, "interactive pack: N=%d Hc=%d A=%d", N, Hc, A);
+    DPT_REQUIRE(tokens && (Hc == 0 || (actions && rewards)), "interactive pack: null pointer");
+    DPT_REQUIRE(N >= 1 && Hc >= 0 && A >= 1, "interactive pack: N=%d Hc=%d A=%d", N, Hc, A);
     const int64_t total = (int64_t)N * (Hc + 1ll) * (A + 3);
     const int64_t blocks = (total + kIaThreads - 1) / kIaThreads;
-    IA_REQUIRE(blocks < (1ll << 31), "interactive pack: %lld elements", (long long)total);
-    hipLaunchKernelGGL(ia_pack_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, ia_stream(stream), actions,
+    DPT_REQUIRE(blocks < (1ll << 31), "interactive pack: %lld elements", (long long)total);
+    hipLaunchKernelGGL(ia_pack_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, as_stream(stream), actions,
                        rewards, N, Hc, A, tokens);
-    return launched_ia("ia_pack");
+    return launched("ia_pack");
 }
 
 int dpt_train_ce_last(const float* preds, const int64_t* targets, int32_t batch, int32_t window, int32_t A,
                       double scale, float* dpreds, double* partial, double* loss_acc, void* stream) {
-    IA_REQUIRE(preds && targets && partial && loss_acc, "train ce last: null pointer");
-    IA_REQUIRE(batch >= 1 && window >= 1 && A >= 1, "train ce last: batch=%d window=%d A=%d", batch, window, A);
-    if (A > kMaxA) {
-        set_error(DPT_EUNSUPPORTED, "train ce last: action_dim=%d above %d", A, kMaxA);
-        return DPT_EUNSUPPORTED;
-    }
+    DPT_REQUIRE(preds && targets && partial && loss_acc, "train ce last: null pointer");
+    DPT_REQUIRE(batch >= 1 && window >= 1 && A >= 1, "train ce last: batch=%d window=%d A=%d", batch, window, A);
+    if (int rc = check_action_dim("train ce last", A)) return rc;
     const int64_t rows = (int64_t)batch * window;
     const int64_t blocks = (rows + kIaThreads - 1) / kIaThreads;
-    IA_REQUIRE(blocks < (1ll << 31), "train ce last: %lld rows", (long long)rows);
-    hipLaunchKernelGGL(ia_ce_last_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, ia_stream(stream), preds,
+    DPT_REQUIRE(blocks < (1ll << 31), "train ce last: %lld rows", (long long)rows);
+    hipLaunchKernelGGL(ia_ce_last_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, as_stream(stream), preds,
                        targets, batch, window, A, scale, dpreds, partial);
-    hipLaunchKernelGGL(ia_ce_finish_kernel, dim3(1), dim3(kIaThreads), 0, ia_stream(stream), partial, batch, scale,
-                       loss_acc);
-    return launched_ia("ia_ce_last");
+    ce_finish(partial, nullptr, batch, scale, loss_acc, as_stream(stream));
+    return launched("ia_ce_last");
 }
 
 int dpt_interactive_workspace_numel(const dpt_train_desc* d, int32_t N, int32_t K, int64_t* numel) {
-    IA_REQUIRE(numel != nullptr, "interactive workspace: null numel");
+    DPT_REQUIRE(numel != nullptr, "interactive workspace: null numel");
     dpt_train_desc run;
     if (int rc = ia_check_shape(d, N, K, 1, "interactive", run)) return rc;
     IaWs w;
@@ -214,18 +171,19 @@ int dpt_interactive_workspace_numel(const dpt_train_desc* d, int32_t N, int32_t 
 }
 
 int dpt_interactive_grad(const dpt_train_desc* d, const float* blob, const dpt_interactive_args* a, void* stream) {
-    IA_REQUIRE(d && blob && a, "interactive grad: null desc / blob / args");
-    IA_REQUIRE(a->means && a->targets && a->workspace && a->dblob && a->loss_acc, "interactive grad: null pointer");
-    IA_REQUIRE(a->K <= 1 || (a->actions_out && a->rewards_out), "interactive grad: null actions_out / rewards_out");
+    DPT_REQUIRE(d && blob && a, "interactive grad: null desc / blob / args");
+    DPT_REQUIRE(a->means && a->targets && a->workspace && a->dblob && a->loss_acc, "interactive grad: null pointer");
+    DPT_REQUIRE(a->K <= 1 || (a->actions_out && a->rewards_out), "interactive grad: null actions_out / rewards_out");
     dpt_train_desc run;
     if (int rc = ia_check_shape(d, a->N, a->K, 1, "interactive", run)) return rc;
     const int base = a->type & ~DPT_BANDIT_F32;
-    IA_REQUIRE(base == DPT_BANDIT_GAUSSIAN || base == DPT_BANDIT_BERNOULLI, "interactive grad: bandit type %d",
-               a->type);
-    IA_REQUIRE((a->flags & ~(DPT_INTERACTIVE_ACCUMULATE | DPT_INTERACTIVE_FULL_WIDTH)) == 0,
-               "interactive grad: unknown flags 0x%x", a->flags);
+    DPT_REQUIRE(base == DPT_BANDIT_GAUSSIAN || base == DPT_BANDIT_BERNOULLI, "interactive grad: bandit type %d",
+                a->type);
+    DPT_REQUIRE((a->flags & ~(DPT_INTERACTIVE_ACCUMULATE | DPT_INTERACTIVE_FULL_WIDTH)) == 0,
+                "interactive grad: unknown flags 0x%x", a->flags);
     const bool accumulate = (a->flags & DPT_INTERACTIVE_ACCUMULATE) != 0;
-    IA_REQUIRE((reinterpret_cast<uintptr_t>(a->workspace) & 15) == 0, "interactive grad: workspace not 16-byte aligned");
+    DPT_REQUIRE((reinterpret_cast<uintptr_t>(a->workspace) & 15) == 0,
+                "interactive grad: workspace not 16-byte aligned");
     IaWs w;
     int64_t nblob = 0;
     if (int rc = ia_ws(&run, w, &nblob)) return rc;

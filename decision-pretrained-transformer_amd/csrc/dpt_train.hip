@@ -890,8 +890,6 @@ __global__ __launch_bounds__(256) void tr_ln_param_part2(const float* __restrict
 
 static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kTrThreads - 1) / kTrThreads); }
 
-static int launched(const char* what) { return check_hip(hipGetLastError(), what); }
-
 int train_dims_check(const TrDims& d) {
     if (d.L < 1 || d.E < 1 || d.E > 1024 || d.F < 1 || d.A < 1 || d.B < 1 || d.T < 1 || d.T > d.npos ||
         (int64_t)d.B * d.T > (1ll << 26)) {
@@ -965,7 +963,11 @@ int rows_reduce_parts(const float* part, int nch, int IN, int OUT, float* dW, fl
 
 // ---- matrix-core dispatch (widths 16, 32, 64; other widths keep the row kernels)
 static bool mm_fast(int E) { return E == 16 || E == 32 || E == 64; }
-enum MmKind { kMmQkv, kMmProj, kMmFc, kMmMp, kMmBdMp, kMmBdFc, kMmBdProj, kMmBdQkv, kMmU, kMmLnQkv, kMmLnFc };
+// the forward products, then the data gradients of the first four in the same order (kMmBdQkv + kind)
+enum MmKind { kMmQkv, kMmProj, kMmFc, kMmMp, kMmU, kMmLnQkv, kMmLnFc, kMmBdQkv, kMmBdProj, kMmBdFc, kMmBdMp };
+// a forward product's IN and OUT in units of E, and whether GELU is applied to its input as it loads
+struct MmShape { int in, out, gelu; };
+constexpr MmShape kMmShape[] = {{1, 3, 0}, {1, 1, 0}, {1, 4, 0}, {4, 1, 1}, {1, 1, 0}, {1, 3, 0}, {1, 4, 0}};
 
 template <class Kern>
 static void allow_lds(Kern k, size_t bytes) {
@@ -1203,6 +1205,48 @@ __global__ void tr_last_rows(const float* __restrict__ src, float* __restrict__ 
     else dst[i] = src[r];
 }
 
+// One forward product of a block on R rows, Y = act(X) W + bias (+ res), IN / OUT / act from its kind
+// (kMmShape): as the row kernel, ...
+static void row_product(int E, int kind, const float* X, const float* W, const float* bias, const float* res, int R,
+                        float* Y, hipStream_t st) {
+    const MmShape k = kMmShape[kind];
+    hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)R * k.out * E)), dim3(kTrThreads), 0, st, X, W, bias, res,
+                       R, k.in * E, k.out * E, k.gelu, Y);
+}
+// ... or the matrix-core form when `fast` (aux = ln_g for the LayerNorm-on-load kinds, which exist in that
+// form alone), ...
+static void fwd_product(int E, int kind, bool fast, const float* X, const float* W, const float* bias,
+                        const float* res, int R, float* Y, hipStream_t st, const float* aux = nullptr) {
+    if (fast) mm(E, kind, X, W, bias, res, aux, R, Y, st);
+    else row_product(E, kind, X, W, bias, res, R, Y, st);
+}
+// ... and with dropout on the way to the residual (site >= 0: never `fast`, the matrix-core forms fuse the
+// residual add and take no mask): Y = res + drop(act(X) W + bias)
+static void fwd_product_res(const TrDims& d, int kind, bool fast, const float* X, const float* W, const float* bias,
+                            const float* res, int R, float* Y, int site, hipStream_t st) {
+    fwd_product(d.E, kind, fast, X, W, bias, site >= 0 ? nullptr : res, R, Y, st);
+    if (site >= 0)
+        hipLaunchKernelGGL(tr_dropout, dim3(blocks_for((int64_t)R * d.E)), dim3(kTrThreads), 0, st, Y, res,
+                           (int64_t)R * d.E, d, site, Y);
+}
+// The backward of forward product `kind` on R rows: the weight gradient of (X, dY) with its reduction into
+// dW | db, then the data gradient dX = dY W^T (kMmMp: times gelu'(X), X = hpre)
+static int bwd_product(int E, int kind, bool fast, const float* X, const float* dY, const float* W, int R,
+                       float* part, float* dW, float* db, float* dX, hipStream_t st) {
+    const MmShape k = kMmShape[kind];
+    const int IN = k.in * E, OUT = k.out * E;
+    const float* hpre = k.gelu ? X : nullptr;
+    if (fast) {
+        if (int rc = wgrad_fast(E, kind, X, dY, R, IN, OUT, part, dW, db, st)) return rc;
+        mm(E, kMmBdQkv + kind, dY, W, nullptr, nullptr, hpre, R, dX, st);
+    } else {
+        if (int rc = wgrad(X, dY, R, IN, OUT, k.gelu, part, dW, db, st)) return rc;
+        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for((int64_t)R * IN)), dim3(kTrThreads), 0, st, dY, W, R, IN,
+                           OUT, hpre, nullptr, dX);
+    }
+    return DPT_OK;
+}
+
 // embeds != nullptr (dpt_train_forward_embeds): x0 = drop(embeds + wpe[t]); tok and the blob's emb_w / emb_b are not read
 int train_forward(const TrDims& d, const float* blob, const float* tok, float* ws, float* preds, hipStream_t st,
                   const float* embeds) {
@@ -1223,119 +1267,30 @@ int train_forward(const TrDims& d, const float* blob, const float* tok, float* w
     else
         hipLaunchKernelGGL(tr_embed, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, tok, blob, d, B, ws + W.x);
     // dropout (GPT2Model in training mode): drop(x0) in place, the attention probabilities, and
-    // c_proj / mlp.c_proj outputs before their residual adds -- on the row kernels, which take the
-    // masks (the matrix-core forms fuse the residual add)
+    // c_proj / mlp.c_proj outputs before their residual adds (fwd_product_res)
     const bool drop = d.drop();
     if (drop) hipLaunchKernelGGL(tr_dropout, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, ws + W.x, nullptr, RE, d, 0,
                                  ws + W.x);
     // slot of layer l's arrays: l, or 0 (x: l & 1) in the forward-only workspace
     auto xs = [&](int l) -> int64_t { return d.fwd_only ? (l & 1) : l; };
-    // DPT_TRAIN_LAST_ONLY (fwd_only == 3, no dropout, T > 1): the last block after its keys and values
-    // for the last position of each sequence alone, then ln_f and the head on those rows
-    const bool last_only = d.fwd_only == 3 && !drop && d.T > 1;
+    const bool fast = mm_fast(E) && !drop;
+    // forward only (nothing saved for a backward): ln_1 / ln_2 applied as the products load their rows
+    const bool ln_in = fast && d.fwd_only;
+    // The last block for the last position of each sequence alone: ln_1 and c_attn on every row (the
+    // block's keys and values), then the last query's attention and everything after it on [B] rows in
+    // the heads of the block's slots, ln_f and the head on those rows, and preds' last rows alone.
+    // DPT_TRAIN_LAST_ONLY (fwd_only == 3, no dropout, T > 1): nothing is saved.
+    // DPT_TRAIN_LAST_LOSS (last_loss_on): y1 / st1 / qkv whole, the row's probabilities [B][T] in the P
+    // slot and the [B]-row o, x2, y2, st2, hpre, x_L, yf, stf stay for the backward.
+    const bool last_loss = last_loss_on(d), last_only = d.fwd_only == 3 && !drop && d.T > 1;
+    const bool last = last_loss || last_only;
+    const int Bn = d.B;
+    const int64_t BE = (int64_t)Bn * E;
     for (int l = 0; l < d.L; ++l) {
         const TrLayer P = TrLayer::make(B.layers + l * d.layer_size(), E);
         const int64_t sl = d.fwd_only ? 0 : l;
-        if (last_loss_on(d) && l == d.L - 1) {
-            // DPT_TRAIN_LAST_LOSS: ln_1 and c_attn on every row (the block's keys and values, saved whole
-            // with y1 / st1 for the backward), then the last query alone: its probabilities [B][T] into the
-            // P slot and [B]-row o, x2, y2, st2, hpre, x_L, yf, stf into the heads of their slots
-            const float* x = ws + W.x + l * RE;
-            float* y1 = ws + W.y1 + l * RE;
-            float* qkv = ws + W.qkv + l * RE * 3;
-            const bool fast = mm_fast(E);
-            layernorm(x, blob + P.ln1_g, blob + P.ln1_b, R, E, y1, ws + W.st1 + (int64_t)l * R * 2, st);
-            if (fast)
-                mm(E, kMmQkv, y1, blob + P.attn_w, blob + P.attn_b, nullptr, nullptr, R, qkv, st);
-            else
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(RE * 3)), dim3(kTrThreads), 0, st, y1, blob + P.attn_w,
-                                   blob + P.attn_b, nullptr, R, E, 3 * E, 0, qkv);
-            const int Bn = d.B;
-            const int64_t BE = (int64_t)Bn * E;
-            float* ol = ws + W.o + l * RE;
-            float* x2l = ws + W.x2 + l * RE;
-            float* y2l = ws + W.y2 + l * RE;
-            float* st2l = ws + W.st2 + (int64_t)l * R * 2;
-            float* hl = ws + W.hpre + l * RE * 4;
-            float* xnl = ws + W.x + (int64_t)d.L * RE;
-            float* xl = ws + W.dx;   // [B][E] the last rows of x (backward scratch, free in the forward)
-            float* pl = ws + W.dh;   // [B][A]
-            const size_t lds = sizeof(float) * rows_per_block * (size_t)(d.T + E);
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(tr_attn_last, dim3((Bn + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), lds, st,
-                               qkv, d, ol, ws + W.P + l * TT);
-            hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, x, xl, Bn, d.T, E, 0);
-            if (fast) {
-                mm(E, kMmProj, ol, blob + P.proj_w, blob + P.proj_b, xl, nullptr, Bn, x2l, st);
-            } else {
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, ol, blob + P.proj_w,
-                                   blob + P.proj_b, xl, Bn, E, E, 0, x2l);
-            }
-            layernorm(x2l, blob + P.ln2_g, blob + P.ln2_b, Bn, E, y2l, st2l, st);
-            if (fast) {
-                mm(E, kMmFc, y2l, blob + P.fc_w, blob + P.fc_b, nullptr, nullptr, Bn, hl, st);
-                mm(E, kMmMp, hl, blob + P.mp_w, blob + P.mp_b, x2l, nullptr, Bn, xnl, st);
-            } else {
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE * 4)), dim3(kTrThreads), 0, st, y2l, blob + P.fc_w,
-                                   blob + P.fc_b, nullptr, Bn, E, 4 * E, 0, hl);
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, hl, blob + P.mp_w,
-                                   blob + P.mp_b, x2l, Bn, 4 * E, E, 1, xnl);
-            }
-            layernorm(xnl, blob + B.lnf_g, blob + B.lnf_b, Bn, E, ws + W.yf, ws + W.stf, st);
-            hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, ws + W.yf,
-                               blob + B.head_w, blob + B.head_b, nullptr, Bn, E, d.A, 0, pl);
-            hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, pl, preds, Bn,
-                               d.T, d.A, 1);
-            return launched("train forward (last-position loss)");
-        }
-        if (last_only && l == d.L - 1) {
-            const float* x = ws + W.x + xs(l) * RE;
-            float* y1 = ws + W.y1;
-            float* qkv = ws + W.qkv;
-            if (mm_fast(E)) {  // ln_1 on load (kMmLnQkv)
-                mm(E, kMmLnQkv, x, blob + P.attn_w, blob + P.attn_b, nullptr, blob + P.ln1_g, R, qkv, st);
-            } else {
-                layernorm(x, blob + P.ln1_g, blob + P.ln1_b, R, E, y1, ws + W.st1, st);
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(RE * 3)), dim3(kTrThreads), 0, st, y1, blob + P.attn_w,
-                                   blob + P.attn_b, nullptr, R, E, 3 * E, 0, qkv);
-            }
-            const int Bn = d.B;
-            const int64_t BE = (int64_t)Bn * E;
-            float* ol = ws + W.o;         // [B][E]
-            float* xl = ws + W.y2;        // [B][E]: the last rows of x
-            float* x2l = ws + W.x2;       // [B][E]
-            float* y2l = ws + W.y1;       // [B][E] (y1 is done with)
-            float* hl = ws + W.hpre;      // [B][4E]
-            float* xnl = ws + W.x + xs(l + 1) * RE;  // [B][E]
-            float* pl = ws + W.hpre + 4 * BE;        // [B][A] (4E (R - B) >= A B for T > 1)
-            const size_t lds = sizeof(float) * rows_per_block * (size_t)(d.T + E);
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(tr_attn_last, dim3((Bn + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), lds, st,
-                               qkv, d, ol, (float*)nullptr);
-            hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, x, xl, Bn, d.T, E, 0);
-            if (mm_fast(E)) {
-                mm(E, kMmProj, ol, blob + P.proj_w, blob + P.proj_b, xl, nullptr, Bn, x2l, st);
-            } else {
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, ol, blob + P.proj_w,
-                                   blob + P.proj_b, xl, Bn, E, E, 0, x2l);
-            }
-            if (mm_fast(E)) {  // ln_2 on load (kMmLnFc)
-                mm(E, kMmLnFc, x2l, blob + P.fc_w, blob + P.fc_b, nullptr, blob + P.ln2_g, Bn, hl, st);
-                mm(E, kMmMp, hl, blob + P.mp_w, blob + P.mp_b, x2l, nullptr, Bn, xnl, st);
-            } else {
-                layernorm(x2l, blob + P.ln2_g, blob + P.ln2_b, Bn, E, y2l, ws + W.st2, st);
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE * 4)), dim3(kTrThreads), 0, st, y2l, blob + P.fc_w,
-                                   blob + P.fc_b, nullptr, Bn, E, 4 * E, 0, hl);
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, hl, blob + P.mp_w,
-                                   blob + P.mp_b, x2l, Bn, 4 * E, E, 1, xnl);
-            }
-            layernorm(xnl, blob + B.lnf_g, blob + B.lnf_b, Bn, E, ws + W.yf, ws + W.stf, st);
-            hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, ws + W.yf,
-                               blob + B.head_w, blob + B.head_b, nullptr, Bn, E, d.A, 0, pl);
-            hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, pl, preds, Bn,
-                               d.T, d.A, 1);
-            return launched("train forward (last position only)");
-        }
+        const bool top = last && l == d.L - 1;
+        const int Rn = top ? Bn : R;  // rows from the attention's output on
         const float* x = ws + W.x + xs(l) * RE;
         float* y1 = ws + W.y1 + sl * RE;
         float* st1 = ws + W.st1 + sl * R * 2;
@@ -1343,146 +1298,48 @@ int train_forward(const TrDims& d, const float* blob, const float* tok, float* w
         float* Pm = d.fwd_only ? nullptr : ws + W.P + sl * TT;
         float* o = ws + W.o + sl * RE;
         float* x2 = ws + W.x2 + sl * RE;
-        float* y2 = ws + W.y2 + sl * RE;
+        float* y2 = last_only && top ? ws + W.y1 : ws + W.y2 + sl * RE;  // (y1 is done with)
         float* st2 = ws + W.st2 + sl * R * 2;
         float* hpre = ws + W.hpre + sl * RE * 4;
         float* xn = ws + W.x + xs(l + 1) * RE;
-        const bool fast = mm_fast(E) && !drop;
-        // forward only (nothing saved for a backward): ln_1 / ln_2 applied as the products load their rows
-        const bool ln_in = fast && d.fwd_only;
+        // top: [B][E] the last rows of x, the c_proj residual (LAST_LOSS: backward scratch, free in the forward)
+        float* xl = last_loss ? ws + W.dx : ws + W.y2;
         if (!ln_in) layernorm(x, blob + P.ln1_g, blob + P.ln1_b, R, E, y1, st1, st);
-        if (ln_in)
-            mm(E, kMmLnQkv, x, blob + P.attn_w, blob + P.attn_b, nullptr, blob + P.ln1_g, R, qkv, st);
-        else if (fast)
-            mm(E, kMmQkv, y1, blob + P.attn_w, blob + P.attn_b, nullptr, nullptr, R, qkv, st);
-        else
-            hipLaunchKernelGGL(tr_linear, dim3(blocks_for(RE * 3)), dim3(kTrThreads), 0, st, y1, blob + P.attn_w,
-                               blob + P.attn_b, nullptr, R, E, 3 * E, 0, qkv);
-        if (fast)
+        fwd_product(E, ln_in ? kMmLnQkv : kMmQkv, fast, ln_in ? x : y1, blob + P.attn_w, blob + P.attn_b, nullptr, R, qkv,
+                    st, ln_in ? blob + P.ln1_g : nullptr);
+        if (top) {
+            if (attn_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds);
+            hipLaunchKernelGGL(tr_attn_last, dim3((Bn + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), attn_lds,
+                               st, qkv, d, o, Pm);
+            hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, x, xl, Bn, d.T, E, 0);
+        } else if (fast) {
             attn_fwd_fast(E, qkv, d, Pm, o, st);
-        else
+        } else {
             hipLaunchKernelGGL(tr_attn_fwd, dim3((R + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), attn_lds,
                                st, qkv, d, drop ? 1 + 3 * l : -1, Pm, o);
-        if (fast)
-            mm(E, kMmProj, o, blob + P.proj_w, blob + P.proj_b, x, nullptr, R, x2, st);
-        else
-            hipLaunchKernelGGL(tr_linear, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, o, blob + P.proj_w,
-                               blob + P.proj_b, drop ? nullptr : x, R, E, E, 0, x2);
-        if (drop)  // x2 = x + drop(o W_proj + b_proj)
-            hipLaunchKernelGGL(tr_dropout, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, x2, x, RE, d, 2 + 3 * l, x2);
-        if (!ln_in) layernorm(x2, blob + P.ln2_g, blob + P.ln2_b, R, E, y2, st2, st);
-        if (ln_in) {
-            mm(E, kMmLnFc, x2, blob + P.fc_w, blob + P.fc_b, nullptr, blob + P.ln2_g, R, hpre, st);
-            mm(E, kMmMp, hpre, blob + P.mp_w, blob + P.mp_b, x2, nullptr, R, xn, st);
-        } else if (fast) {
-            mm(E, kMmFc, y2, blob + P.fc_w, blob + P.fc_b, nullptr, nullptr, R, hpre, st);
-            mm(E, kMmMp, hpre, blob + P.mp_w, blob + P.mp_b, x2, nullptr, R, xn, st);
-        } else {
-            hipLaunchKernelGGL(tr_linear, dim3(blocks_for(RE * 4)), dim3(kTrThreads), 0, st, y2, blob + P.fc_w,
-                               blob + P.fc_b, nullptr, R, E, 4 * E, 0, hpre);
-            hipLaunchKernelGGL(tr_linear, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, hpre, blob + P.mp_w,
-                               blob + P.mp_b, drop ? nullptr : x2, R, 4 * E, E, 1, xn);
-            if (drop)  // x_{l+1} = x2 + drop(gelu(hpre) W_mp + b_mp)
-                hipLaunchKernelGGL(tr_dropout, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, xn, x2, RE, d, 3 + 3 * l,
-                                   xn);
         }
+        // x2 = x + drop(o W_proj + b_proj), x_{l+1} = x2 + drop(gelu(hpre) W_mp + b_mp)
+        fwd_product_res(d, kMmProj, fast, o, blob + P.proj_w, blob + P.proj_b, top ? xl : x, Rn, x2, drop ? 2 + 3 * l : -1,
+                        st);
+        if (!ln_in) layernorm(x2, blob + P.ln2_g, blob + P.ln2_b, Rn, E, y2, st2, st);
+        fwd_product(E, ln_in ? kMmLnFc : kMmFc, fast, ln_in ? x2 : y2, blob + P.fc_w, blob + P.fc_b, nullptr, Rn, hpre, st,
+                    ln_in ? blob + P.ln2_g : nullptr);
+        fwd_product_res(d, kMmMp, fast, hpre, blob + P.mp_w, blob + P.mp_b, x2, Rn, xn, drop ? 3 + 3 * l : -1, st);
         if (int rc = launched("train forward layer")) return rc;
     }
-    layernorm(ws + W.x + xs(d.L) * RE, blob + B.lnf_g, blob + B.lnf_b, R, E, ws + W.yf, ws + W.stf, st);
-    hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)R * d.A)), dim3(kTrThreads), 0, st, ws + W.yf,
-                       blob + B.head_w, blob + B.head_b, nullptr, R, E, d.A, 0, preds);
-    return launched("train forward head");
-}
-
-// DPT_TRAIN_LAST_LOSS (last_loss_on): everything above the last block's c_attn for the B last rows.
-// Compact [B]-row scratch: dx -> W.dx, dy -> W.dy, dout -> W.dout, dh -> W.dh, dx2 -> W.dh + 4BE,
-// dpreds' last rows -> W.dh + 5BE (5BE + BA <= 4RE since T >= 2 and A <= 3E).  Leaves dx (R, E) =
-// dL/dx_{L-1}, as an iteration of train_backward's loop does.
-static int train_backward_last_top(const TrDims& d, const TrBlob& B, const TrWs& W, const float* blob, float* ws,
-                                   const float* dpreds, float* dblob, hipStream_t st) {
-    const int R = d.R(), E = d.E, Bn = d.B, l = d.L - 1;
-    const int64_t RE = (int64_t)R * E, BE = (int64_t)Bn * E, TT = (int64_t)d.B * d.T * TrWs::tpad(d.T);
-    const int rows_per_block = kTrThreads / 64;
-    const unsigned row_blocks = (R + rows_per_block - 1) / rows_per_block;
-    const unsigned brow_blocks = (Bn + rows_per_block - 1) / rows_per_block;
-    const TrLayer P = TrLayer::make(B.layers + l * d.layer_size(), E);
-    const TrLayer G = P;  // same offsets in dblob
-    float* part = ws + W.part;
-    float* dx = ws + W.dx;
-    float* dy = ws + W.dy;
-    float* dout = ws + W.dout;
-    float* dh = ws + W.dh;
-    float* dx2 = ws + W.dh + 4 * BE;
-    float* dpl = ws + W.dh + 5 * BE;
-    float* dqkv = ws + W.dqkv;
-    const float* x = ws + W.x + l * RE;
-    const float* y1 = ws + W.y1 + l * RE;
-    const float* st1 = ws + W.st1 + (int64_t)l * R * 2;
-    const float* qkv = ws + W.qkv + l * RE * 3;
-    const float* Prow = ws + W.P + l * TT;
-    const float* ol = ws + W.o + l * RE;
-    const float* x2l = ws + W.x2 + l * RE;
-    const float* y2l = ws + W.y2 + l * RE;
-    const float* st2l = ws + W.st2 + (int64_t)l * R * 2;
-    const float* hl = ws + W.hpre + l * RE * 4;
-    const float* xnl = ws + W.x + (int64_t)d.L * RE;
-    const bool fast = mm_fast(E);
-    hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, dpreds, dpl, Bn, d.T,
-                       d.A, 0);
-    // head and ln_f
-    if (int rc = wgrad(ws + W.yf, dpl, Bn, E, d.A, 0, part, dblob + B.head_w, dblob + B.head_b, st)) return rc;
-    hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dpl, blob + B.head_w, Bn, E,
-                       d.A, nullptr, nullptr, dy);
-    if (int rc = ln_param_grad(xnl, ws + W.stf, dy, Bn, E, part, dblob + B.lnf_g, dblob + B.lnf_b, st)) return rc;
-    hipLaunchKernelGGL(tr_layernorm_bwd, dim3(brow_blocks), dim3(kTrThreads), 0, st, xnl, ws + W.stf, blob + B.lnf_g, dy,
-                       Bn, E, nullptr, dx);
-    // MLP and ln_2
-    if (fast) {
-        if (int rc = wgrad_fast(E, kMmMp, hl, dx, Bn, 4 * E, E, part, dblob + G.mp_w, dblob + G.mp_b, st)) return rc;
-        mm(E, kMmBdMp, dx, blob + P.mp_w, nullptr, nullptr, hl, Bn, dh, st);
-        if (int rc = wgrad_fast(E, kMmFc, y2l, dh, Bn, E, 4 * E, part, dblob + G.fc_w, dblob + G.fc_b, st)) return rc;
-        mm(E, kMmBdFc, dh, blob + P.fc_w, nullptr, nullptr, nullptr, Bn, dy, st);
-    } else {
-        if (int rc = wgrad(hl, dx, Bn, 4 * E, E, 1, part, dblob + G.mp_w, dblob + G.mp_b, st)) return rc;
-        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(BE * 4)), dim3(kTrThreads), 0, st, dx, blob + P.mp_w, Bn,
-                           4 * E, E, hl, nullptr, dh);
-        if (int rc = wgrad(y2l, dh, Bn, E, 4 * E, 0, part, dblob + G.fc_w, dblob + G.fc_b, st)) return rc;
-        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dh, blob + P.fc_w, Bn, E,
-                           4 * E, nullptr, nullptr, dy);
-    }
-    if (int rc = ln_param_grad(x2l, st2l, dy, Bn, E, part, dblob + G.ln2_g, dblob + G.ln2_b, st)) return rc;
-    hipLaunchKernelGGL(tr_layernorm_bwd, dim3(brow_blocks), dim3(kTrThreads), 0, st, x2l, st2l, blob + P.ln2_g, dy, Bn, E,
-                       dx, dx2);
-    // c_proj, then the one query row's attention
-    if (fast) {
-        if (int rc = wgrad_fast(E, kMmProj, ol, dx2, Bn, E, E, part, dblob + G.proj_w, dblob + G.proj_b, st)) return rc;
-        mm(E, kMmBdProj, dx2, blob + P.proj_w, nullptr, nullptr, nullptr, Bn, dout, st);
-    } else {
-        if (int rc = wgrad(ol, dx2, Bn, E, E, 0, part, dblob + G.proj_w, dblob + G.proj_b, st)) return rc;
-        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dx2, blob + P.proj_w, Bn, E,
-                           E, nullptr, nullptr, dout);
-    }
-    const size_t lds = sizeof(float) * rows_per_block * ((size_t)d.T + 2 * (size_t)E);
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(tr_attn_last_bwd, dim3(brow_blocks), dim3(kTrThreads), lds, st, qkv, Prow, ol, dout, d, dqkv);
-    // the residual x2 = x + ...: dL/dx2 is dx2 at the last rows and 0 elsewhere, at full width
-    float* dx2f = ws + W.dx2;
-    if (int rc = check_hip(hipMemsetAsync(dx2f, 0, sizeof(float) * RE, st), "dx2 memset")) return rc;
-    hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dx2, dx2f, Bn, d.T, E, 1);
-    // c_attn and ln_1 on every row
-    float* dyf = ws + W.dy;
-    if (fast) {
-        if (int rc = wgrad_fast(E, kMmQkv, y1, dqkv, R, E, 3 * E, part, dblob + G.attn_w, dblob + G.attn_b, st)) return rc;
-        mm(E, kMmBdQkv, dqkv, blob + P.attn_w, nullptr, nullptr, nullptr, R, dyf, st);
-    } else {
-        if (int rc = wgrad(y1, dqkv, R, E, 3 * E, 0, part, dblob + G.attn_w, dblob + G.attn_b, st)) return rc;
-        hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dqkv, blob + P.attn_w, R, E,
-                           3 * E, nullptr, nullptr, dyf);
-    }
-    if (int rc = ln_param_grad(x, st1, dyf, R, E, part, dblob + G.ln1_g, dblob + G.ln1_b, st)) return rc;
-    hipLaunchKernelGGL(tr_layernorm_bwd, dim3(row_blocks), dim3(kTrThreads), 0, st, x, st1, blob + P.ln1_g, dyf, R, E,
-                       dx2f, dx);
-    return launched("train backward (last-position loss)");
+    // ln_f and the head; after a last-position block on its [B] rows, into [B][A] scratch (LAST_LOSS: W.dh, as
+    // xl; LAST_ONLY: behind the [B][4E] hpre rows, 4E (R - B) >= A B for T > 1) scattered into preds' last rows
+    const int Rh = last ? Bn : R;
+    float* pl = !last ? preds : last_loss ? ws + W.dh : ws + W.hpre + 4 * BE;
+    layernorm(ws + W.x + xs(d.L) * RE, blob + B.lnf_g, blob + B.lnf_b, Rh, E, ws + W.yf, ws + W.stf, st);
+    hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)Rh * d.A)), dim3(kTrThreads), 0, st, ws + W.yf,
+                       blob + B.head_w, blob + B.head_b, nullptr, Rh, E, d.A, 0, pl);
+    if (last)
+        hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, pl, preds, Bn,
+                           d.T, d.A, 1);
+    return launched(last_loss ? "train forward (last-position loss)"
+                    : last    ? "train forward (last position only)"
+                              : "train forward head");
 }
 
 // dembeds != nullptr (dpt_train_backward_embeds): dL/dx0 after the site-0 mask goes to dembeds (R, E) and the
@@ -1492,38 +1349,51 @@ int train_backward(const TrDims& d, const float* blob, const float* tok, float* 
     if (int rc = train_dims_check(d)) return rc;
     const TrBlob B = TrBlob::make(d);
     const TrWs W = TrWs::make(d);
-    const int R = d.R(), E = d.E;
-    const int64_t RE = (int64_t)R * E, TT = (int64_t)d.B * d.T * TrWs::tpad(d.T);
+    const int R = d.R(), E = d.E, Bn = d.B;
+    const int64_t RE = (int64_t)R * E, BE = (int64_t)Bn * E, TT = (int64_t)d.B * d.T * TrWs::tpad(d.T);
     const int rows_per_block = kTrThreads / 64;
-    const unsigned row_blocks = (R + rows_per_block - 1) / rows_per_block;
+    auto row_blocks = [&](int rows) { return dim3((rows + rows_per_block - 1) / rows_per_block); };
     float* part = ws + W.part;
     float* dx = ws + W.dx;
     float* dx2 = ws + W.dx2;
     float* dy = ws + W.dy;
+    float* dh = ws + W.dh;
+    float* dqkv = ws + W.dqkv;
+    float* dout = ws + W.dout;
+    float* dS = ws + W.dS;
     if (int rc = check_hip(hipMemsetAsync(dblob, 0, sizeof(float) * B.total, st), "dblob memset")) return rc;
-    int top = d.L - 1;  // the first block of the full-width loop below
-    if (last_loss_on(d)) {
-        // DPT_TRAIN_LAST_LOSS: the head, ln_f and the last block's MLP, ln_2 and c_proj on the [B] last
-        // rows the forward saved; the attention backward of the one query row per sequence fills every
-        // row of dqkv; from c_attn down the block runs at full width and joins the loop
-        if (int rc = train_backward_last_top(d, B, W, blob, ws, dpreds, dblob, st)) return rc;
-        top = d.L - 2;
-    } else {
-    // head: preds = yf head_w + head_b
-    if (int rc = wgrad(ws + W.yf, dpreds, R, E, d.A, 0, part, dblob + B.head_w, dblob + B.head_b, st)) return rc;
-    hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dpreds, blob + B.head_w, R, E,
-                       d.A, nullptr, nullptr, dy);
-    // ln_f
-    if (int rc = ln_param_grad(ws + W.x + d.L * RE, ws + W.stf, dy, R, E, part, dblob + B.lnf_g, dblob + B.lnf_b, st))
-        return rc;
-    hipLaunchKernelGGL(tr_layernorm_bwd, dim3(row_blocks), dim3(kTrThreads), 0, st, ws + W.x + d.L * RE, ws + W.stf,
-                       blob + B.lnf_g, dy, R, E, nullptr, dx);
+    // DPT_TRAIN_LAST_LOSS (last_loss_on): the head, ln_f and the last block's MLP, ln_2 and c_proj on the [B]
+    // last rows the forward saved; the attention backward of the one query row per sequence fills every
+    // row of dqkv; from c_attn down the block runs at full width, as every block below it.  Compact
+    // [B]-row scratch: dx, dy, dout and dh in the heads of their slots, dx2 -> W.dh + 4BE, dpreds' last
+    // rows -> W.dh + 5BE (5BE + BA <= 4RE since T >= 2 and A <= 3E).
+    const bool last = last_loss_on(d);
+    const int Rh = last ? Bn : R;
+    const float* dp = dpreds;
+    if (last) {
+        float* dpl = ws + W.dh + 5 * BE;
+        hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, dpreds, dpl, Bn, d.T,
+                           d.A, 0);
+        dp = dpl;
     }
+    // head: preds = yf head_w + head_b
+    if (int rc = wgrad(ws + W.yf, dp, Rh, E, d.A, 0, part, dblob + B.head_w, dblob + B.head_b, st)) return rc;
+    hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for((int64_t)Rh * E)), dim3(kTrThreads), 0, st, dp,
+                       blob + B.head_w, Rh, E, d.A, nullptr, nullptr, dy);
+    // ln_f
+    if (int rc = ln_param_grad(ws + W.x + d.L * RE, ws + W.stf, dy, Rh, E, part, dblob + B.lnf_g, dblob + B.lnf_b, st))
+        return rc;
+    hipLaunchKernelGGL(tr_layernorm_bwd, row_blocks(Rh), dim3(kTrThreads), 0, st, ws + W.x + d.L * RE, ws + W.stf,
+                       blob + B.lnf_g, dy, Rh, E, nullptr, dx);
     const size_t ds_lds = sizeof(float) * rows_per_block * (size_t)E;
     const bool drop = d.drop();
-    for (int l = top; l >= 0; --l) {
+    const bool fast = mm_fast(E) && !drop;
+    for (int l = d.L - 1; l >= 0; --l) {
         const TrLayer P = TrLayer::make(B.layers + l * d.layer_size(), E);
-        const TrLayer G = TrLayer::make(B.layers + l * d.layer_size(), E);  // same offsets in dblob
+        const TrLayer G = P;  // same offsets in dblob
+        const bool top = last && l == d.L - 1;
+        const int Rn = top ? Bn : R;                 // rows above the attention
+        float* dx2n = top ? ws + W.dh + 4 * BE : dx2;  // dL/dx2 on those rows
         const float* x = ws + W.x + l * RE;
         const float* y1 = ws + W.y1 + l * RE;
         const float* st1 = ws + W.st1 + (int64_t)l * R * 2;
@@ -1534,11 +1404,6 @@ int train_backward(const TrDims& d, const float* blob, const float* tok, float* 
         const float* y2 = ws + W.y2 + l * RE;
         const float* st2 = ws + W.st2 + (int64_t)l * R * 2;
         const float* hpre = ws + W.hpre + l * RE * 4;
-        float* dh = ws + W.dh;
-        float* dqkv = ws + W.dqkv;
-        float* dout = ws + W.dout;
-        float* dS = ws + W.dS;
-        const bool fast = mm_fast(E) && !drop;
         // MLP: x_{l+1} = x2 + drop(gelu(hpre) W_mp + b_mp), hpre = y2 W_fc + b_fc; with dropout the
         // product's gradient dx keep (into dy, free until the LayerNorm input gradient below)
         const float* dmp = dx;
@@ -1547,60 +1412,48 @@ int train_backward(const TrDims& d, const float* blob, const float* tok, float* 
                                dy);
             dmp = dy;
         }
-        if (fast) {
-            if (int rc = wgrad_fast(E, kMmMp, hpre, dx, R, 4 * E, E, part, dblob + G.mp_w, dblob + G.mp_b, st)) return rc;
-            mm(E, kMmBdMp, dx, blob + P.mp_w, nullptr, nullptr, hpre, R, dh, st);
-            if (int rc = wgrad_fast(E, kMmFc, y2, dh, R, E, 4 * E, part, dblob + G.fc_w, dblob + G.fc_b, st)) return rc;
-            mm(E, kMmBdFc, dh, blob + P.fc_w, nullptr, nullptr, nullptr, R, dy, st);
-        } else {
-            if (int rc = wgrad(hpre, dmp, R, 4 * E, E, 1, part, dblob + G.mp_w, dblob + G.mp_b, st)) return rc;
-            hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(RE * 4)), dim3(kTrThreads), 0, st, dmp, blob + P.mp_w,
-                               R, 4 * E, E, hpre, nullptr, dh);
-            if (int rc = wgrad(y2, dh, R, E, 4 * E, 0, part, dblob + G.fc_w, dblob + G.fc_b, st)) return rc;
-            hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dh, blob + P.fc_w, R,
-                               E, 4 * E, nullptr, nullptr, dy);
-        }
-        if (int rc = ln_param_grad(x2, st2, dy, R, E, part, dblob + G.ln2_g, dblob + G.ln2_b, st)) return rc;
-        hipLaunchKernelGGL(tr_layernorm_bwd, dim3(row_blocks), dim3(kTrThreads), 0, st, x2, st2, blob + P.ln2_g, dy, R, E,
-                           dx, dx2);
+        if (int rc = bwd_product(E, kMmMp, fast, hpre, dmp, blob + P.mp_w, Rn, part, dblob + G.mp_w, dblob + G.mp_b, dh, st))
+            return rc;
+        if (int rc = bwd_product(E, kMmFc, fast, y2, dh, blob + P.fc_w, Rn, part, dblob + G.fc_w, dblob + G.fc_b, dy, st))
+            return rc;
+        if (int rc = ln_param_grad(x2, st2, dy, Rn, E, part, dblob + G.ln2_g, dblob + G.ln2_b, st)) return rc;
+        hipLaunchKernelGGL(tr_layernorm_bwd, row_blocks(Rn), dim3(kTrThreads), 0, st, x2, st2, blob + P.ln2_g, dy, Rn, E,
+                           dx, dx2n);
         // attention: x2 = x + drop(o W_proj + b_proj)
-        const float* dpj = dx2;
+        const float* dpj = dx2n;
         if (drop) {
-            hipLaunchKernelGGL(tr_dropout, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dx2, nullptr, RE, d, 2 + 3 * l,
+            hipLaunchKernelGGL(tr_dropout, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dx2n, nullptr, RE, d, 2 + 3 * l,
                                dy);
             dpj = dy;
         }
-        if (fast) {
-            if (int rc = wgrad_fast(E, kMmProj, o, dx2, R, E, E, part, dblob + G.proj_w, dblob + G.proj_b, st)) return rc;
-            mm(E, kMmBdProj, dx2, blob + P.proj_w, nullptr, nullptr, nullptr, R, dout, st);
-        } else {
-            if (int rc = wgrad(o, dpj, R, E, E, 0, part, dblob + G.proj_w, dblob + G.proj_b, st)) return rc;
-            hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dpj, blob + P.proj_w,
-                               R, E, E, nullptr, nullptr, dout);
-        }
-        if (fast) {
+        if (int rc = bwd_product(E, kMmProj, fast, o, dpj, blob + P.proj_w, Rn, part, dblob + G.proj_w, dblob + G.proj_b,
+                                 dout, st))
+            return rc;
+        if (top) {
+            // the one query row's attention, then the residual x2 = x + ...: dL/dx2 is dx2n at the last rows
+            // and 0 elsewhere, at full width
+            const size_t lds = sizeof(float) * rows_per_block * ((size_t)d.T + 2 * (size_t)E);
+            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(tr_attn_last_bwd, row_blocks(Bn), dim3(kTrThreads), lds, st, qkv, Pm, o, dout, d, dqkv);
+            if (int rc = check_hip(hipMemsetAsync(dx2, 0, sizeof(float) * RE, st), "dx2 memset")) return rc;
+            hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dx2n, dx2, Bn, d.T, E, 1);
+        } else if (fast) {
             attn_bwd_fast(E, qkv, Pm, o, dout, d, dS, dqkv, st);
         } else {
             const int site = drop ? 1 + 3 * l : -1;
-            hipLaunchKernelGGL(tr_attn_bwd_ds, dim3(row_blocks), dim3(kTrThreads), ds_lds, st, qkv, Pm, o, dout, d, site,
-                               dS);
+            hipLaunchKernelGGL(tr_attn_bwd_ds, row_blocks(R), dim3(kTrThreads), ds_lds, st, qkv, Pm, o, dout, d, site, dS);
             hipLaunchKernelGGL(tr_attn_bwd_dq, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, qkv, dS, d, dqkv);
             hipLaunchKernelGGL(tr_attn_bwd_dkv, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, qkv, Pm, dS, dout, d, site,
                                dqkv);
         }
-        if (fast) {
-            if (int rc = wgrad_fast(E, kMmQkv, y1, dqkv, R, E, 3 * E, part, dblob + G.attn_w, dblob + G.attn_b, st))
-                return rc;
-            mm(E, kMmBdQkv, dqkv, blob + P.attn_w, nullptr, nullptr, nullptr, R, dy, st);
-        } else {
-            if (int rc = wgrad(y1, dqkv, R, E, 3 * E, 0, part, dblob + G.attn_w, dblob + G.attn_b, st)) return rc;
-            hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dqkv, blob + P.attn_w,
-                               R, E, 3 * E, nullptr, nullptr, dy);
-        }
+        // c_attn and ln_1, on every row
+        if (int rc = bwd_product(E, kMmQkv, fast, y1, dqkv, blob + P.attn_w, R, part, dblob + G.attn_w, dblob + G.attn_b, dy,
+                                 st))
+            return rc;
         if (int rc = ln_param_grad(x, st1, dy, R, E, part, dblob + G.ln1_g, dblob + G.ln1_b, st)) return rc;
-        hipLaunchKernelGGL(tr_layernorm_bwd, dim3(row_blocks), dim3(kTrThreads), 0, st, x, st1, blob + P.ln1_g, dy, R, E,
-                           dx2, dx);
-        if (int rc = launched("train backward layer")) return rc;
+        hipLaunchKernelGGL(tr_layernorm_bwd, row_blocks(R), dim3(kTrThreads), 0, st, x, st1, blob + P.ln1_g, dy, R, E, dx2,
+                           dx);
+        if (int rc = launched(top ? "train backward (last-position loss)" : "train backward layer")) return rc;
     }
     // embedding: x0 = drop(tok emb_w + emb_b + wpe[t])
     if (drop) hipLaunchKernelGGL(tr_dropout, dim3(blocks_for(RE)), dim3(kTrThreads), 0, st, dx, nullptr, RE, d, 0, dx);
@@ -1699,56 +1552,12 @@ __global__ void gen_embed(const float* __restrict__ tok, const float* __restrict
     x[i] = acc + blob[b.wpe + (int64_t)pos * d.E + e];
 }
 
-// One wave per task: store the new token's key and value at position pos of the task's cache
-// (rows [pos][E] of [N][H][E]) and attend over positions 0..pos -- tr_attn_fwd's arithmetic for the
-// causal row of the new token (the new key and value are read from the qkv row itself).
-__global__ void gen_attn_decode(const float* __restrict__ qkv, float* __restrict__ Kc, float* __restrict__ Vc, int E,
-                                int N, int H, int pos, float* __restrict__ O) {
-    extern __shared__ float sm[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int task = blockIdx.x * (blockDim.x / 64) + wave;
-    if (task >= N) return;
-    float* pr = sm + (size_t)wave * (H + E);
-    float* q = pr + H;
-    const float* row = qkv + (int64_t)task * 3 * E;
-    float* K = Kc + (int64_t)task * H * E;
-    float* V = Vc + (int64_t)task * H * E;
-    for (int e = lane; e < E; e += 64) {
-        q[e] = row[e];
-        K[(int64_t)pos * E + e] = row[E + e];
-        V[(int64_t)pos * E + e] = row[2 * E + e];
-    }
-    wave_lds_sync();
-    const float scale = 1.0f / sqrtf((float)E);
-    float m = -INFINITY;
-    for (int j = lane; j <= pos; j += 64) {
-        const float* k = j == pos ? row + E : K + (int64_t)j * E;
-        float s = 0.f;
-        for (int e = 0; e < E; ++e) s = fmaf(q[e], k[e], s);
-        s *= scale;
-        pr[j] = s;
-        m = fmaxf(m, s);
-    }
-    m = wave_max(m);
-    float l = 0.f;
-    for (int j = lane; j <= pos; j += 64) {
-        const float p = expf(pr[j] - m);
-        pr[j] = p;
-        l += p;
-    }
-    const float inv = 1.0f / wave_sum(l);
-    for (int j = lane; j <= pos; j += 64) pr[j] *= inv;
-    wave_lds_sync();
-    for (int e = lane; e < E; e += 64) {
-        float acc = 0.f;
-        for (int j = 0; j < pos; ++j) acc = fmaf(pr[j], V[(int64_t)j * E + e], acc);
-        acc = fmaf(pr[pos], row[2 * E + e], acc);
-        O[(int64_t)task * E + e] = acc;
-    }
-}
-
-// gen_attn_decode in the folded-attention form (GenFold): u scores the cached y rows (and the new
-// position's own y, at yn), the output is the attention-weighted y (c_proj runs on Wvp)
+// The folded attention (GenFold) of the new token, one wave per task: store the token's y row (yn) at
+// position pos of the task's cache (rows [pos][E] of [N][H][E]) and attend over positions 0..pos with
+// the query u -- the scores are u . y_j / sqrt(E) over the cached rows and the new position's own row
+// (read from yn itself), the output is the attention-weighted y (c_proj runs on Wvp).  tr_attn_fwd's
+// arithmetic for the causal row of the new token: lanes stride over the keys with the columns in
+// order, then over the columns with the keys in order.  LDS per wave: H + E floats.
 __global__ void gen_attn_ydecode(const float* __restrict__ u, const float* __restrict__ yn, float* __restrict__ Yc,
                                  int E, int N, int H, int pos, float* __restrict__ O) {
     extern __shared__ float sm[];
@@ -1792,80 +1601,14 @@ __global__ void gen_attn_ydecode(const float* __restrict__ u, const float* __res
     }
 }
 
-// The same for E % 4 == 0, E <= 256, with the rows read as float4: LPK lanes per key (a power of
-// two >= E / 4), 64 / LPK keys per wave-instruction, so every key row is one coalesced read.  Scores
-// are 4-term partial dots summed over the key's lanes by xor shuffles; the values accumulate per
-// lane group (keys kq, kq + KPW, ...) and the groups are summed at the end: a different fp32
-// order than gen_attn_decode (and tr_attn_fwd), the same softmax.
-template <int LPK>
-__global__ void gen_attn_decode4(const float* __restrict__ qkv, float* __restrict__ Kc, float* __restrict__ Vc, int E,
-                                 int N, int H, int pos, float* __restrict__ O) {
-    constexpr int KPW = 64 / LPK;
-    extern __shared__ float sm[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int task = blockIdx.x * (blockDim.x / 64) + wave;
-    if (task >= N) return;
-    float* pr = sm + (size_t)wave * H;
-    const int E4 = E >> 2, c = lane % LPK, kq = lane / LPK;
-    const bool act = c < E4;
-    const float* row = qkv + (int64_t)task * 3 * E;
-    const floatx4* K4 = reinterpret_cast<const floatx4*>(Kc + (int64_t)task * H * E);
-    const floatx4* V4 = reinterpret_cast<const floatx4*>(Vc + (int64_t)task * H * E);
-    const floatx4 zero = {0.f, 0.f, 0.f, 0.f};
-    const floatx4 q = act ? reinterpret_cast<const floatx4*>(row)[c] : zero;
-    const floatx4 kn = act ? reinterpret_cast<const floatx4*>(row + E)[c] : zero;
-    const floatx4 vn = act ? reinterpret_cast<const floatx4*>(row + 2 * E)[c] : zero;
-    if (kq == 0 && act) {
-        reinterpret_cast<floatx4*>(Kc + (int64_t)task * H * E)[(int64_t)pos * E4 + c] = kn;
-        reinterpret_cast<floatx4*>(Vc + (int64_t)task * H * E)[(int64_t)pos * E4 + c] = vn;
-    }
-    const float scale = 1.0f / sqrtf((float)E);
-    float m = -INFINITY;
-    for (int jb = 0; jb <= pos; jb += KPW) {
-        const int j = jb + kq;
-        floatx4 k = zero;
-        if (act && j < pos) k = K4[(int64_t)j * E4 + c];
-        else if (act && j == pos) k = kn;
-        float d = fmaf(q[0], k[0], fmaf(q[1], k[1], fmaf(q[2], k[2], q[3] * k[3])));
-#pragma unroll
-        for (int x = 1; x < LPK; x <<= 1) d += __shfl_xor(d, x, 64);
-        if (j <= pos) {
-            d *= scale;
-            if (c == 0) pr[j] = d;
-            m = fmaxf(m, d);
-        }
-    }
-    m = wave_max(m);
-    wave_lds_sync();
-    float l = 0.f;
-    for (int j = lane; j <= pos; j += 64) {
-        const float p = expf(pr[j] - m);
-        pr[j] = p;
-        l += p;
-    }
-    const float inv = 1.0f / wave_sum(l);
-    wave_lds_sync();
-    floatx4 acc = zero;
-    for (int jb = 0; jb <= pos; jb += KPW) {
-        const int j = jb + kq;
-        if (!act || j > pos) continue;
-        const floatx4 v = j == pos ? vn : V4[(int64_t)j * E4 + c];
-        const float p = pr[j];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = fmaf(p, v[r], acc[r]);
-    }
-#pragma unroll
-    for (int x = LPK; x < 64; x <<= 1)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] += __shfl_xor(acc[r], x, 64);
-    if (kq == 0 && act) reinterpret_cast<floatx4*>(O + (int64_t)task * E)[c] = acc * inv;
-}
-
-// The folded-attention form of gen_attn_decode4 (GenFold), one pass over the y cache (flash decoding):
-// lane group kq takes keys kq, kq + KPW, ... (LPK lanes per key, one float4 of the row each), kU keys
-// of the group per iteration (kU rows in flight per lane), and keeps its own softmax state (m, l, acc)
-// in the exp2 domain; the KPW groups are merged at the end by xor shuffles.  Each y row is read once
-// (the two-pass form read it for the scores and again for the weighted sum).  No LDS.
+// The same for E % 4 == 0, E <= 256, with the rows read as float4, in one pass over the y cache (flash
+// decoding): LPK lanes per key (a power of two >= E / 4, one float4 of the row each), 64 / LPK = KPW keys
+// per wave-instruction, so every key row is one coalesced read.  Scores are 4-term partial dots summed
+// over the key's lanes by xor shuffles.  Lane group kq takes keys kq, kq + KPW, ..., kU keys of the group
+// per iteration (kU rows in flight per lane), and keeps its own softmax state (m, l, acc) in the exp2
+// domain; the KPW groups are merged at the end by xor shuffles.  Each y row is read once, for its score
+// and for the weighted sum.  A different fp32 summation order than gen_attn_ydecode (and tr_attn_fwd),
+// the same softmax.  No LDS.
 template <int LPK>
 __global__ void gen_attn_ydecode4(const float* __restrict__ u, const float* __restrict__ yn, float* __restrict__ Yc,
                                   int E, int N, int H, int pos, float* __restrict__ O) {
@@ -2019,22 +1762,30 @@ int rollout_bandit_generic(const TrDims& d, const float* blob, const dpt_bandit_
     const int rows_per_block = kTrThreads / 64;
     const unsigned row_blocks = (N + rows_per_block - 1) / rows_per_block;
     // the float4 attention for E % 4 == 0 up to 256 (LPK lanes per key), else the scalar one
-    const int lpk = E % 4 ? 0 : E <= 16 ? 4 : E <= 32 ? 8 : E <= 64 ? 16 : E <= 128 ? 32 : E <= 256 ? 64 : 0;
-    const void* attn_k = lpk == 4    ? (const void*)gen_attn_ydecode4<4>
-                         : lpk == 8  ? (const void*)gen_attn_ydecode4<8>
-                         : lpk == 16 ? (const void*)gen_attn_ydecode4<16>
-                         : lpk == 32 ? (const void*)gen_attn_ydecode4<32>
-                         : lpk == 64 ? (const void*)gen_attn_ydecode4<64>
-                                     : (const void*)gen_attn_ydecode;
-    const size_t attn_lds = lpk ? 0 : sizeof(float) * rows_per_block * (size_t)(H + E);  // (the float4 form: none)
+    using AttnKernel = void (*)(const float*, const float*, float*, int, int, int, int, float*);
+    const AttnKernel attn_k = E % 4 || E > 256 ? gen_attn_ydecode
+                              : E <= 16        ? gen_attn_ydecode4<4>
+                              : E <= 32        ? gen_attn_ydecode4<8>
+                              : E <= 64        ? gen_attn_ydecode4<16>
+                              : E <= 128       ? gen_attn_ydecode4<32>
+                                               : gen_attn_ydecode4<64>;
+    // the scalar form's dynamic LDS (the float4 form: none)
+    const size_t attn_lds = attn_k == gen_attn_ydecode ? sizeof(float) * rows_per_block * (size_t)(H + E) : 0;
     if (attn_lds > 160 * 1024) {
         set_error(DPT_EUNSUPPORTED, "generic bandit rollout: H=%d too long for the attention kernel", H);
         return DPT_EUNSUPPORTED;
     }
-    if (attn_lds > 64 * 1024) (void)hipFuncSetAttribute(attn_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds);
+    if (attn_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds);
     GenEnv g{N, H, a.A, 1, a.type, a.sample, a.first_task, a.var, a.seed, a.counter, a.means, a.uniforms, a.noise,
              a.actions_out, a.rewards_out, a.arm_value_out, a.logits_out, env ? *env : GenEnvAct{nullptr, 0, nullptr}};
-    const bool fast = mm_dec_fast(E);  // the column-split matrix-core products (mm_dec)
+    // the column-split matrix-core products (mm_dec) or the row kernels; ln_2 on load where mm_dec has it
+    // (bit-identical to the separate LayerNorm)
+    const bool fast = mm_dec_fast(E), ln_in = fast && mm_ln_in_ok(E);
+    auto product = [&](int kind, const float* X, const float* Wt, const float* bias, const float* res, float* Y,
+                       const float* aux = nullptr) {
+        if (fast) mm_dec(E, kind, X, Wt, bias, res, N, Y, st, aux);
+        else row_product(E, kind, X, Wt, bias, res, N, Y, st);
+    };
     float* x = ws + W.x;
     float* x2 = ws + W.x2;
     float* y = ws + W.y;
@@ -2056,38 +1807,14 @@ int rollout_bandit_generic(const TrDims& d, const float* blob, const dpt_bandit_
             const float* F = ws + W.fold + l * GenFold::size(E);
             const float *G = F, *Wvp = F + (int64_t)E * E, *g0 = F + 2ll * E * E, *bvp = g0 + E;
             float* uq = qkv;
-            if (fast)
-                mm_dec(E, kMmU, y, G, g0, nullptr, N, uq, st);
-            else
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(NE)), dim3(kTrThreads), 0, st, y, G, g0, nullptr, N, E, E, 0,
-                                   uq);
-            float* Yc = ws + W.Y + l * cache;
-            switch (lpk) {
-                case 4: hipLaunchKernelGGL(gen_attn_ydecode4<4>, dim3(row_blocks), dim3(kTrThreads), attn_lds, st, uq, y, Yc, E, N, H, h, o); break;
-                case 8: hipLaunchKernelGGL(gen_attn_ydecode4<8>, dim3(row_blocks), dim3(kTrThreads), attn_lds, st, uq, y, Yc, E, N, H, h, o); break;
-                case 16: hipLaunchKernelGGL(gen_attn_ydecode4<16>, dim3(row_blocks), dim3(kTrThreads), attn_lds, st, uq, y, Yc, E, N, H, h, o); break;
-                case 32: hipLaunchKernelGGL(gen_attn_ydecode4<32>, dim3(row_blocks), dim3(kTrThreads), attn_lds, st, uq, y, Yc, E, N, H, h, o); break;
-                case 64: hipLaunchKernelGGL(gen_attn_ydecode4<64>, dim3(row_blocks), dim3(kTrThreads), attn_lds, st, uq, y, Yc, E, N, H, h, o); break;
-                default: hipLaunchKernelGGL(gen_attn_ydecode, dim3(row_blocks), dim3(kTrThreads), attn_lds, st, uq, y, Yc, E, N, H, h, o);
-            }
-            if (fast)
-                mm_dec(E, kMmProj, o, Wvp, bvp, x, N, x2, st);
-            else
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(NE)), dim3(kTrThreads), 0, st, o, Wvp, bvp, x, N, E, E, 0, x2);
-            if (fast && mm_ln_in_ok(E)) {  // ln_2 on load (bit-identical to the separate LayerNorm)
-                mm_dec(E, kMmLnFc, x2, blob + P.fc_w, blob + P.fc_b, nullptr, N, hb, st, blob + P.ln2_g);
-                mm_dec(E, kMmMp, hb, blob + P.mp_w, blob + P.mp_b, x2, N, x, st);
-            } else if (fast) {
-                layernorm(x2, blob + P.ln2_g, blob + P.ln2_b, N, E, y, stt, st);
-                mm_dec(E, kMmFc, y, blob + P.fc_w, blob + P.fc_b, nullptr, N, hb, st);
-                mm_dec(E, kMmMp, hb, blob + P.mp_w, blob + P.mp_b, x2, N, x, st);
-            } else {
-                layernorm(x2, blob + P.ln2_g, blob + P.ln2_b, N, E, y, stt, st);
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(NE * 4)), dim3(kTrThreads), 0, st, y, blob + P.fc_w,
-                                   blob + P.fc_b, nullptr, N, E, 4 * E, 0, hb);
-                hipLaunchKernelGGL(tr_linear, dim3(blocks_for(NE)), dim3(kTrThreads), 0, st, hb, blob + P.mp_w,
-                                   blob + P.mp_b, x2, N, 4 * E, E, 1, x);
-            }
+            product(kMmU, y, G, g0, nullptr, uq);
+            hipLaunchKernelGGL(attn_k, dim3(row_blocks), dim3(kTrThreads), attn_lds, st, uq, y, ws + W.Y + l * cache, E,
+                               N, H, h, o);
+            product(kMmProj, o, Wvp, bvp, x, x2);
+            if (!ln_in) layernorm(x2, blob + P.ln2_g, blob + P.ln2_b, N, E, y, stt, st);
+            product(ln_in ? kMmLnFc : kMmFc, ln_in ? x2 : y, blob + P.fc_w, blob + P.fc_b, nullptr, hb,
+                    ln_in ? blob + P.ln2_g : nullptr);
+            product(kMmMp, hb, blob + P.mp_w, blob + P.mp_b, x2, x);
         }
         layernorm(x, blob + B.lnf_g, blob + B.lnf_b, N, E, y, stt, st);
         hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)N * d.A)), dim3(kTrThreads), 0, st, y, blob + B.head_w,

@@ -14,17 +14,6 @@ namespace dpt {
 
 constexpr int kTsThreads = 256;
 
-#define TS_REQUIRE(cond, ...)                      \
-    do {                                           \
-        if (!(cond)) {                             \
-            set_error(DPT_EINVAL, __VA_ARGS__);    \
-            return DPT_EINVAL;                     \
-        }                                          \
-    } while (0)
-
-static hipStream_t ts_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static int64_t round4(int64_t n) { return (n + 3) & ~int64_t(3); }
-
 // ----------------------------------------------------------------------------- pack
 // One thread per output float.  tokens (B, T, F): row 0 = [query | 0], row 1 + j = transition
 // perm[b][j] (or j) of sample index[b] as [s | a | s' | r]; then targets (B, A).  A sample or
@@ -110,19 +99,27 @@ __global__ __launch_bounds__(kTsThreads) void ts_ce_kernel(const float* __restri
     if (threadIdx.x == 0) partial[b] = red[0];
 }
 
-// *acc += sum_b partial[b], one workgroup: thread-strided sums, then the same LDS tree
-__global__ __launch_bounds__(kTsThreads) void ts_ce_finish_kernel(const double* __restrict__ partial, int B,
-                                                                  double* __restrict__ acc) {
+// *acc += scale * sum_i w_i values[i] (dpt_common.h ce_finish), one workgroup: thread-strided sums, then
+// the same LDS tree.  A weight or a scale of 1.0 is exact in fp64: the plain sum of ts_ce_kernel's partials.
+__global__ __launch_bounds__(kTsThreads) void ce_finish_kernel(const double* __restrict__ values,
+                                                               const double* __restrict__ weights, int64_t n,
+                                                               double scale, double* __restrict__ acc) {
     __shared__ double red[kTsThreads];
     double s = 0.0;
-    for (int b = threadIdx.x; b < B; b += kTsThreads) s += partial[b];
+    for (int64_t i = threadIdx.x; i < n; i += kTsThreads) {
+        const double w = weights ? weights[i] : 1.0;
+        if (w != 0.0) s += w * values[i];
+    }
     red[threadIdx.x] = s;
     __syncthreads();
     for (int w = kTsThreads / 2; w > 0; w >>= 1) {
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) *acc += red[0];
+    if (threadIdx.x == 0) *acc += scale * red[0];
+}
+void ce_finish(const double* values, const double* weights, int64_t n, double scale, double* acc, hipStream_t st) {
+    hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(kTsThreads), 0, st, values, weights, n, scale, acc);
 }
 
 // ----------------------------------------------------------------------------- AdamW
@@ -169,8 +166,6 @@ __global__ __launch_bounds__(kTsThreads) void ts_adamw_kernel(float* __restrict_
     if (e < numel) adam_one(p[e], g[e], m[e], v[e], c);
 }
 
-static int launched_ts(const char* what) { return check_hip(hipGetLastError(), what); }
-
 // workspace of dpt_train_step for desc.batch sequences (floats; every region 16-byte aligned)
 struct StepWs {
     int64_t train, tokens, targets, preds, dpreds, dblob, partial, total;
@@ -193,9 +188,9 @@ static int step_ws(const dpt_train_desc* d, StepWs& w) {
 }
 
 static int check_step_args(const dpt_train_desc* d, const dpt_train_data* data, const int64_t* index, int32_t batch) {
-    TS_REQUIRE(d && data && index, "null desc / data / index");
-    TS_REQUIRE(batch >= 1 && batch <= d->batch, "batch=%d outside 1..desc.batch=%d", batch, d->batch);
-    TS_REQUIRE(d->reserved == 0, "train step: desc flags must be 0 (got 0x%x)", d->reserved);
+    DPT_REQUIRE(d && data && index, "null desc / data / index");
+    DPT_REQUIRE(batch >= 1 && batch <= d->batch, "batch=%d outside 1..desc.batch=%d", batch, d->batch);
+    DPT_REQUIRE(d->reserved == 0, "train step: desc flags must be 0 (got 0x%x)", d->reserved);
     return DPT_OK;
 }
 
@@ -207,48 +202,44 @@ extern "C" {
 
 int dpt_train_pack_batch(const dpt_train_desc* d, const dpt_train_data* data, const int64_t* index,
                          const int64_t* perm, int32_t batch, float* tokens, float* targets, void* stream) {
-    TS_REQUIRE(d && data && index && tokens && targets, "train pack: null pointer");
-    TS_REQUIRE(data->query_states && data->context_states && data->context_actions && data->context_next_states &&
-                   data->context_rewards && data->optimal_actions,
-               "train pack: null dataset array");
-    TS_REQUIRE(batch >= 1 && d->state_dim >= 1 && d->action_dim >= 1 && data->n >= 1 && data->horizon >= 0,
-               "train pack: batch=%d sd=%d A=%d n=%lld horizon=%d", batch, d->state_dim, d->action_dim,
-               (long long)data->n, data->horizon);
-    TS_REQUIRE((int64_t)d->window == 1 + (int64_t)data->horizon, "train pack: desc.window=%d != 1 + horizon=%d",
-               d->window, data->horizon);
+    DPT_REQUIRE(d && data && index && tokens && targets, "train pack: null pointer");
+    DPT_REQUIRE(data->query_states && data->context_states && data->context_actions && data->context_next_states &&
+                    data->context_rewards && data->optimal_actions,
+                "train pack: null dataset array");
+    DPT_REQUIRE(batch >= 1 && d->state_dim >= 1 && d->action_dim >= 1 && data->n >= 1 && data->horizon >= 0,
+                "train pack: batch=%d sd=%d A=%d n=%lld horizon=%d", batch, d->state_dim, d->action_dim,
+                (long long)data->n, data->horizon);
+    DPT_REQUIRE((int64_t)d->window == 1 + (int64_t)data->horizon, "train pack: desc.window=%d != 1 + horizon=%d",
+                d->window, data->horizon);
     const int64_t F = 2 * (int64_t)d->state_dim + d->action_dim + 1;
     const int64_t total = (int64_t)batch * d->window * F + (int64_t)batch * d->action_dim;
-    TS_REQUIRE((total + kTsThreads - 1) / kTsThreads < (1ll << 31), "train pack: %lld elements", (long long)total);
+    DPT_REQUIRE((total + kTsThreads - 1) / kTsThreads < (1ll << 31), "train pack: %lld elements", (long long)total);
     hipLaunchKernelGGL(ts_pack_kernel, dim3((unsigned)((total + kTsThreads - 1) / kTsThreads)), dim3(kTsThreads), 0,
-                       ts_stream(stream), *data, index, perm, batch, d->window, d->state_dim, d->action_dim, tokens,
+                       as_stream(stream), *data, index, perm, batch, d->window, d->state_dim, d->action_dim, tokens,
                        targets);
-    return launched_ts("ts_pack");
+    return launched("ts_pack");
 }
 
 int dpt_train_ce_loss(const float* preds, const float* targets, int32_t batch, int32_t window, int32_t A,
                       float* dpreds, double* partial, double* loss_acc, void* stream) {
-    TS_REQUIRE(preds && targets && partial && loss_acc, "train ce: null pointer");
-    TS_REQUIRE(batch >= 1 && window >= 1 && A >= 1, "train ce: batch=%d window=%d A=%d", batch, window, A);
-    if (A > kMaxA) {
-        set_error(DPT_EUNSUPPORTED, "train ce: action_dim=%d above %d", A, kMaxA);
-        return DPT_EUNSUPPORTED;
-    }
-    hipLaunchKernelGGL(ts_ce_kernel, dim3(batch), dim3(kTsThreads), 0, ts_stream(stream), preds, targets, window, A,
+    DPT_REQUIRE(preds && targets && partial && loss_acc, "train ce: null pointer");
+    DPT_REQUIRE(batch >= 1 && window >= 1 && A >= 1, "train ce: batch=%d window=%d A=%d", batch, window, A);
+    if (int rc = check_action_dim("train ce", A)) return rc;
+    hipLaunchKernelGGL(ts_ce_kernel, dim3(batch), dim3(kTsThreads), 0, as_stream(stream), preds, targets, window, A,
                        dpreds, partial);
-    hipLaunchKernelGGL(ts_ce_finish_kernel, dim3(1), dim3(kTsThreads), 0, ts_stream(stream), partial, batch,
-                       loss_acc);
-    return launched_ts("ts_ce");
+    ce_finish(partial, nullptr, batch, 1.0, loss_acc, as_stream(stream));
+    return launched("ts_ce");
 }
 
 int dpt_adamw_step(float* blob, const float* dblob, float* m, float* v, int64_t numel, const dpt_adamw_args* a,
                    void* stream) {
-    TS_REQUIRE(blob && dblob && m && v && a, "adamw: null pointer");
-    TS_REQUIRE(numel >= 0, "adamw: numel=%lld", (long long)numel);
-    TS_REQUIRE(a->step >= 1, "adamw: step=%lld (the first step is 1)", (long long)a->step);
-    TS_REQUIRE(a->lr >= 0.0 && a->eps >= 0.0 && a->weight_decay >= 0.0 && a->beta1 >= 0.0 && a->beta1 < 1.0 &&
-                   a->beta2 >= 0.0 && a->beta2 < 1.0,
-               "adamw: lr=%g betas=(%g, %g) eps=%g weight_decay=%g", a->lr, a->beta1, a->beta2, a->eps,
-               a->weight_decay);
+    DPT_REQUIRE(blob && dblob && m && v && a, "adamw: null pointer");
+    DPT_REQUIRE(numel >= 0, "adamw: numel=%lld", (long long)numel);
+    DPT_REQUIRE(a->step >= 1, "adamw: step=%lld (the first step is 1)", (long long)a->step);
+    DPT_REQUIRE(a->lr >= 0.0 && a->eps >= 0.0 && a->weight_decay >= 0.0 && a->beta1 >= 0.0 && a->beta1 < 1.0 &&
+                    a->beta2 >= 0.0 && a->beta2 < 1.0,
+                "adamw: lr=%g betas=(%g, %g) eps=%g weight_decay=%g", a->lr, a->beta1, a->beta2, a->eps,
+                a->weight_decay);
     if (numel == 0) return DPT_OK;
     const double bc1 = 1.0 - std::pow(a->beta1, (double)a->step);
     const double bc2 = 1.0 - std::pow(a->beta2, (double)a->step);
@@ -258,14 +249,14 @@ int dpt_adamw_step(float* blob, const float* dblob, float* m, float* v, int64_t 
     const int64_t n4 = aligned ? numel / 4 : 0;
     const int64_t threads = n4 + (numel - 4 * n4);
     const int64_t blocks = (threads + kTsThreads - 1) / kTsThreads;
-    TS_REQUIRE(blocks < (1ll << 31), "adamw: numel=%lld", (long long)numel);
-    hipLaunchKernelGGL(ts_adamw_kernel, dim3((unsigned)blocks), dim3(kTsThreads), 0, ts_stream(stream), blob, dblob,
+    DPT_REQUIRE(blocks < (1ll << 31), "adamw: numel=%lld", (long long)numel);
+    hipLaunchKernelGGL(ts_adamw_kernel, dim3((unsigned)blocks), dim3(kTsThreads), 0, as_stream(stream), blob, dblob,
                        m, v, n4, numel, c);
-    return launched_ts("ts_adamw");
+    return launched("ts_adamw");
 }
 
 int dpt_train_step_workspace_numel(const dpt_train_desc* d, int64_t* numel) {
-    TS_REQUIRE(d && numel, "train step workspace: null pointer");
+    DPT_REQUIRE(d && numel, "train step workspace: null pointer");
     StepWs w;
     if (int rc = step_ws(d, w)) return rc;
     *numel = w.total;
@@ -276,14 +267,11 @@ int dpt_train_step(const dpt_train_desc* d, const dpt_train_data* data, const in
                    int32_t batch, float* blob, float* m, float* v, const dpt_adamw_args* opt, float* ws,
                    double* loss_acc, void* stream) {
     if (int rc = check_step_args(d, data, index, batch)) return rc;
-    TS_REQUIRE(blob && m && v && opt && ws && loss_acc, "train step: null pointer");
-    TS_REQUIRE(opt->step >= 1, "train step: step=%lld (the first step is 1)", (long long)opt->step);
-    if (d->action_dim > kMaxA) {
-        set_error(DPT_EUNSUPPORTED, "train step: action_dim=%d above %d", d->action_dim, kMaxA);
-        return DPT_EUNSUPPORTED;
-    }
-    TS_REQUIRE((int64_t)d->window == 1 + (int64_t)data->horizon, "train step: desc.window=%d != 1 + horizon=%d",
-               d->window, data->horizon);
+    DPT_REQUIRE(blob && m && v && opt && ws && loss_acc, "train step: null pointer");
+    DPT_REQUIRE(opt->step >= 1, "train step: step=%lld (the first step is 1)", (long long)opt->step);
+    if (int rc = check_action_dim("train step", d->action_dim)) return rc;
+    DPT_REQUIRE((int64_t)d->window == 1 + (int64_t)data->horizon, "train step: desc.window=%d != 1 + horizon=%d",
+                d->window, data->horizon);
     StepWs w;
     if (int rc = step_ws(d, w)) return rc;  // laid out for desc.batch; a smaller batch uses a prefix of each region
     int64_t nblob = 0;
@@ -293,7 +281,7 @@ int dpt_train_step(const dpt_train_desc* d, const dpt_train_data* data, const in
     float *tokens = ws + w.tokens, *targets = ws + w.targets, *preds = ws + w.preds, *dpreds = ws + w.dpreds;
     float* dblob = ws + w.dblob;
     double* partial = reinterpret_cast<double*>(ws + w.partial);
-    TS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "train step: workspace not 16-byte aligned");
+    DPT_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "train step: workspace not 16-byte aligned");
     if (int rc = dpt_train_pack_batch(&run, data, index, perm, batch, tokens, targets, stream)) return rc;
     if (int rc = dpt_train_forward(&run, blob, tokens, ws + w.train, preds, stream)) return rc;
     if (int rc = dpt_train_ce_loss(preds, targets, batch, run.window, run.action_dim, dpreds, partial, loss_acc,
@@ -307,16 +295,13 @@ int dpt_train_eval_loss(const dpt_train_desc* d, const dpt_train_data* data, con
                         const int64_t* perm, int32_t batch, const float* blob, float* ws, double* loss_acc,
                         void* stream) {
     if (int rc = check_step_args(d, data, index, batch)) return rc;
-    TS_REQUIRE(blob && ws && loss_acc, "train eval loss: null pointer");
-    if (d->action_dim > kMaxA) {
-        set_error(DPT_EUNSUPPORTED, "train eval loss: action_dim=%d above %d", d->action_dim, kMaxA);
-        return DPT_EUNSUPPORTED;
-    }
-    TS_REQUIRE((int64_t)d->window == 1 + (int64_t)data->horizon, "train eval loss: desc.window=%d != 1 + horizon=%d",
-               d->window, data->horizon);
+    DPT_REQUIRE(blob && ws && loss_acc, "train eval loss: null pointer");
+    if (int rc = check_action_dim("train eval loss", d->action_dim)) return rc;
+    DPT_REQUIRE((int64_t)d->window == 1 + (int64_t)data->horizon, "train eval loss: desc.window=%d != 1 + horizon=%d",
+                d->window, data->horizon);
     StepWs w;
     if (int rc = step_ws(d, w)) return rc;
-    TS_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "train eval loss: workspace not 16-byte aligned");
+    DPT_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "train eval loss: workspace not 16-byte aligned");
     dpt_train_desc run = *d;
     run.batch = batch;
     run.reserved = DPT_TRAIN_FORWARD_ONLY;  // every position's preds: never DPT_TRAIN_LAST_ONLY

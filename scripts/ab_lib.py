@@ -4,7 +4,14 @@ An argument libX.so:<bytes> runs libX.so with dpt_hip.set_cache_budget(<bytes>);
 runs it with dpt_hip.set_block0_mfma(True / False); +nows / +nomemo run DarkRoom without the
 layer-0 workspace / the logits memo (suffixes in that order: lib.so+nows+nomemo); a last suffix
 +y32 / +y24 sets dpt_hip.set_ycache_bits (a build without that key fails when it is set).
-Env: AB_H, AB_N, AB_A, AB_TILE, AB_ROUNDS."""
+Env: AB_H, AB_N, AB_A, AB_TILE, AB_ROUNDS.
+AB_WL=train: the training entry points instead (trunk forward / backward, generic rollout, the three
+cross-entropies, the fused steps): one sha1 per case over the raw bytes of every output, then the ms
+per dpt_train_step at the shapes of scripts/train_timing.py (AB_STEPS steps between device events).
+The parent exits 1 when two libraries' digests differ and writes digests.txt / ab.json to AB_OUT
+(default profiles/train_refactor)."""
+import ctypes
+import hashlib
 import json
 import os
 import subprocess
@@ -13,6 +20,178 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def sha(*tensors):
+    h = hashlib.sha1()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()[:16]
+
+
+def train_digests():
+    """{case: sha1} of every output the training entry points write, each case seeded."""
+    import torch
+    from types import SimpleNamespace
+    from dpt_hip import _lib, _p, _stream
+    import dpt_hip.train as tr
+    from models.net import Transformer
+    out = {}
+    dev = torch.device("cuda")
+
+    def rnd(rs, *shape, scale=1.0):
+        return torch.from_numpy((rs.standard_normal(shape) * scale).astype(np.float32)).to(dev)
+
+    # 1. the trunk, through the token and the embeds entry
+    sd, A, L, B = 1, 5, 2, 3
+    FO, LO, LL = tr.FORWARD_ONLY, tr.LAST_ONLY, tr.LAST_LOSS
+    for E in (16, 18, 32, 48, 64):
+        for T in (1, 2, 65):
+            for flags, p in ((0, 0.0), (FO, 0.0), (FO | LO, 0.0), (LL, 0.0), (0, 0.1), (FO, 0.1)):
+                rs = np.random.RandomState(1000 * E + 10 * T + flags)
+                d = tr.desc(L, E, sd, A, 72, B, T, flags=flags, dropout=p, seed=4242)
+                blob = rnd(rs, tr._numel("dpt_train_blob_numel", d), scale=0.1)
+                dp = rnd(rs, B, T, A)
+                if flags & LL:
+                    dp[:, :-1] = 0
+                for entry, x in (("tokens", rnd(rs, B, T, 2 * sd + A + 1)), ("embeds", rnd(rs, B, T, E))):
+                    preds, ws = (tr.forward if entry == "tokens" else tr.forward_embeds)(d, blob, x)
+                    outs = [preds[:, -1] if flags & (LO | LL) else preds]  # the last-position modes write that row alone
+                    if not flags & FO:
+                        outs += [tr.backward(d, blob, x, ws, dp)] if entry == "tokens" else \
+                            list(tr.backward_embeds(d, blob, ws, dp))
+                    out[f"trunk E{E} T{T} flags{flags} drop{p} {entry}"] = sha(*outs)
+    # 2. the generic rollout past one 64-key lap
+    N, H = 9, 70
+    for E in (16, 18, 48, 64, 128):
+        for name, code in (("gaussian", _lib.BANDIT_GAUSSIAN), ("bernoulli", _lib.BANDIT_BERNOULLI)):
+            rs = np.random.RandomState(7 * E + code)
+            shape = SimpleNamespace(n_layer=L, n_embd=E, state_dim=1, action_dim=A, n_positions=72)
+            blob = rnd(rs, tr._numel("dpt_train_blob_numel", tr.desc(L, E, 1, A, 72, 1, 1)), scale=0.1)
+            o = tr.rollout_bandit_generic(shape, rs.uniform(0, 1, (N, A)), H, 0.3, True, code, seed=11,
+                                          want_logits=True, blob=blob)
+            out[f"rollout E{E} {name}"] = sha(o["actions"], o["rewards"], o["logits"])
+    # 3. the loss kernels: one target out of range, one weight 0
+    for B_, T_, A_ in ((3, 1, 5), (4, 9, 20), (2, 5, 1)):
+        rs = np.random.RandomState(100 * B_ + A_)
+        preds = rnd(rs, B_, T_, A_, scale=3.0)
+        soft = torch.eye(A_, device=dev)[torch.from_numpy(rs.randint(0, A_, B_)).to(dev)].contiguous()
+        tseq = torch.from_numpy(rs.randint(0, A_, B_)).to(dev)
+        tseq[0] = A_
+        trow = torch.from_numpy(rs.randint(0, A_, (B_, T_)).astype(np.int32)).to(dev)
+        trow[-1, -1] = -1
+        w = torch.from_numpy(rs.uniform(0.5, 2.0, (B_, T_))).to(dev)
+        w[0, 0] = 0.0
+        sc = ctypes.c_double(1.0 / B_)
+
+        def bufs(rows):
+            return (torch.zeros_like(preds), torch.zeros(rows, dtype=torch.float64, device=dev),
+                    torch.full((1,), 0.5, dtype=torch.float64, device=dev))
+
+        dpr, part, acc = bufs(B_)
+        _lib.call("dpt_train_ce_loss", _p(preds), _p(soft), B_, T_, A_, _p(dpr), _p(part), _p(acc), _stream())
+        out[f"ce_loss {B_} {T_} {A_}"] = sha(dpr, part, acc)
+        dpr, part, acc = bufs(B_)
+        _lib.call("dpt_train_ce_last", _p(preds), _p(tseq), B_, T_, A_, sc, _p(dpr), _p(part), _p(acc), _stream())
+        out[f"ce_last {B_} {T_} {A_}"] = sha(dpr, part, acc)
+        for form, ts, tw, ww in (("seq", tseq, None, None), ("row weighted", None, trow, w)):
+            dpr, part, acc = bufs(B_ * T_)
+            _lib.call("dpt_train_ce_rows", _p(preds), _p(ts), _p(tw), _p(ww), B_, T_, A_, sc, _p(part), _p(dpr),
+                      _p(acc), _stream())
+            out[f"ce_rows {form} {B_} {T_} {A_}"] = sha(dpr, part, acc)
+    # 4. the fused steps (the blobs after AdamW, the gradient blobs, the losses)
+    for E in (32, 18):
+        def model(seed, H_):
+            torch.manual_seed(seed)
+            return Transformer(dict(horizon=H_, state_dim=1, action_dim=A, n_layer=L, n_embd=E, n_head=1, dropout=0.0,
+                                    test=False)).cuda().train()
+
+        rs = np.random.RandomState(E)
+        t = tr.Trainer(model(1, 8), lr=1e-3)
+        t.step(step_data(rs, 12, 8, 1, A), np.arange(2, 8))
+        out[f"train_step E{E}"] = sha(t.blob, t.m, t.v, t.loss)
+        means = rs.uniform(0, 1, (8, A))
+        for chunk in (0, 3):  # 3: the later chunks accumulate
+            t = tr.InteractiveTrainer(model(2, 8), lr=1e-3, chunk=chunk)
+            acts, rew = t.step(means, 6, 0.3, "uniform", seed=5)
+            out[f"interactive E{E} chunk{chunk}"] = sha(t.blob, t.dblob, t.loss, acts, rew)
+        t = tr.ExploreExploitTrainer(model(3, 8), model(4, 8), lr=1e-3)
+        recs = t.step(means, 6, 0.3, "bernoulli", 0.5, seed=6)
+        out[f"explore E{E}"] = sha(t.explorer_blob, t.exploiter_blob, t.explorer_dblob, t.exploiter_dblob,
+                                   t.loss_explorer, t.loss_exploiter, *recs)
+    return out
+
+
+def step_data(rs, n, H, sd, A):
+    import torch
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
+    return {"query_states": f32(rs.randint(0, 10, (n, sd))), "context_states": f32(rs.randint(0, 10, (n, H, sd))),
+            "context_actions": f32(np.eye(A)[rs.randint(0, A, (n, H))]),
+            "context_next_states": f32(rs.randint(0, 10, (n, H, sd))),
+            "context_rewards": f32(rs.normal(0.5, 0.5, (n, H, 1))),
+            "optimal_actions": f32(np.eye(A)[rs.randint(0, A, n)])}
+
+
+def train_child(lib):
+    """AB_WL=train: the digests, then ms per dpt_train_step (forward, cross-entropy, backward, AdamW) at
+    scripts/train_timing.py's shapes -- width 32, 4 layers, batch 64."""
+    import torch
+    import dpt_hip.train as tr
+    from models.net import Transformer
+    digests = train_digests() if os.environ.get("AB_DIGEST", "1") == "1" else {}
+    steps, ms = int(os.environ.get("AB_STEPS", "300")), {}
+    for name, sd, A, H, B in (("bandit_T501", 1, 5, 500, 64), ("darkroom_T101", 2, 5, 100, 64)):
+        torch.manual_seed(0)
+        rs = np.random.RandomState(0)
+        t = tr.Trainer(Transformer(dict(horizon=H, state_dim=sd, action_dim=A, n_layer=4, n_embd=32, n_head=1,
+                                        dropout=0.0, test=False)).cuda().train(), lr=1e-4)
+        dd = t.device_data(step_data(rs, 4 * B, H, sd, A))
+        idx = [torch.from_numpy(rs.randint(0, 4 * B, B)).cuda() for _ in range(16)]
+        for i in range(20):
+            t.step(dd, idx[i % 16])
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(steps):
+            t.step(dd, idx[i % 16])
+        b.record()
+        torch.cuda.synchronize()
+        ms[name] = a.elapsed_time(b) / steps
+    print(json.dumps({"lib": lib, "digests": digests, "ms": ms}))
+
+
+def train_parent(libs):
+    """Alternating rounds of train_child; one summary line, digests.txt and ab.json under AB_OUT."""
+    rounds, dig = {lib: [] for lib in libs}, {}
+    same = True
+    for rnd in range(int(os.environ.get("AB_ROUNDS", "2"))):
+        for lib in libs:
+            cp = subprocess.run([sys.executable, __file__, "--child", lib], capture_output=True, text=True,
+                                timeout=300)
+            if cp.returncode:
+                sys.exit(f"{lib}: child failed ({cp.returncode})\n{cp.stderr[-3000:]}")
+            d = json.loads(cp.stdout.strip().splitlines()[-1])
+            rounds[lib].append(d["ms"])
+            same = same and dig.setdefault(lib, d["digests"]) == d["digests"]  # the same library, run to run
+    ref = dig[libs[0]]
+    diff = sorted(k for lib in libs for k in set(ref) | set(dig[lib]) if ref.get(k) != dig[lib].get(k))
+    res = {"digest_cases": len(ref), "digests_equal": same and not diff, "differing": diff,
+           "steps_per_round": int(os.environ.get("AB_STEPS", "300")), "ms_per_step": {}}
+    for lib, rs_ in rounds.items():
+        res["ms_per_step"][lib] = {
+            shape: {"rounds": [round(r[shape], 5) for r in rs_], "median": float(np.median([r[shape] for r in rs_])),
+                    "min": min(r[shape] for r in rs_), "max": max(r[shape] for r in rs_)} for shape in rs_[0]}
+    out = os.environ.get("AB_OUT", os.path.join(ROOT, "profiles", "train_refactor"))
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, "digests.txt"), "w") as f:
+        for k in ref:
+            f.write("  ".join([dig[lib].get(k, "-") for lib in dig] + [k]) + "\n")
+        f.write("# columns: " + "  ".join(dig) + "  case\n")
+    with open(os.path.join(out, "ab.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    sys.exit(0 if res["digests_equal"] else 1)
 
 
 def child(lib):
@@ -31,6 +210,8 @@ def child(lib):
     nows = lib.endswith("+nows")  # DarkRoom without the per-episode layer-0 workspace
     lib = lib[: -len("+nows")] if nows else lib
     _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.__file__), lib.split(":")[0])
+    if os.environ.get("AB_WL") == "train":
+        return train_child(lib)
     import torch
     import bench
     import dpt_hip
@@ -91,6 +272,8 @@ if __name__ == "__main__":
     if len(sys.argv) > 2 and sys.argv[1] == "--child":
         child(sys.argv[2])
         sys.exit(0)
+    if os.environ.get("AB_WL") == "train":
+        train_parent(sys.argv[1:])  # one library given twice: its own round-to-round spread
     res = {lib: [] for lib in sys.argv[1:]}
     chk = {}
     for rnd in range(int(os.environ.get("AB_ROUNDS", "2"))):
