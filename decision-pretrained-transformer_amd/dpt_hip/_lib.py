@@ -296,3 +296,25 @@ SIGNATURES["dpt_image_front_backward"] = (_i32, [_image_desc_p, _c_void_p, _c_vo
 SIGNATURES["dpt_train_forward_embeds"] = (_i32, [_train_desc_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p])
 SIGNATURES["dpt_train_backward_embeds"] = (_i32, [_train_desc_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                                   _c_void_p, _c_void_p])
+
+
+IMAGE_RAW_DTYPES = {"float64": 0, "float32": 1}  # dpt_image_normalize's dtype codes
+
+
+class ImageData(ctypes.Structure):
+    """dpt_image_data: the fp32 image training set on the device (dataset.py's ``ImageDataset``)."""
+    _fields_ = [("n", _i64), ("horizon", _i32), ("image_size", _i32), ("query_states", _c_void_p),
+                ("context_states", _c_void_p), ("context_actions", _c_void_p), ("context_rewards", _c_void_p),
+                ("optimal_actions", _c_void_p), ("query_images", _c_void_p), ("context_images", _c_void_p)]
+
+
+_image_data_p = ctypes.POINTER(ImageData)
+SIGNATURES["dpt_image_normalize"] = (_i32, [_c_void_p, _i32, _i64, _c_void_p, _c_void_p])
+SIGNATURES["dpt_image_pack_batch"] = (_i32, [_train_desc_p, _image_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                             _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_image_train_step_workspace_numel"] = (_i32, [_train_desc_p, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_image_train_step"] = (_i32, [_train_desc_p, _image_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                             _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                             ctypes.POINTER(AdamWArgs), _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_image_train_eval_loss"] = (_i32, [_train_desc_p, _image_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                                  _c_void_p, _c_void_p, _c_void_p, _c_void_p])

@@ -24,9 +24,15 @@ window packed from its records, forward, last-position cross-entropy, backward; 
 (dpt_explore_grad per chunk of envs: the explorer's rollout with the env stepped apart, one pack, the
 exploiter's and the explorer's forward / every-position cross-entropy / backward with the advantage
 weights in between; then dpt_adamw_step for each model).
+
+``DeviceImageData`` / ``ImageTrainer`` are the fused step that train_miniworld.py --fused runs
+(dpt_image_train_step: the batch gathered from a device-resident, device-normalised image set, the
+image front end, the trunk, summed cross-entropy, both backwards, dpt_adamw_step on the trunk blob and
+on the front blob).
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -482,6 +488,217 @@ class Trainer:
         params = param_list(self.model)
         with torch.no_grad():
             for p, w in zip(params, _unpack(self.blob, [p.shape for p in params], [p.dtype for p in params])):
+                p.copy_(w)
+        return self.model
+
+
+IMAGE_DATA_KEYS = ("query_states", "context_states", "context_actions", "context_rewards", "optimal_actions")
+
+
+def normalize_images(raw, out=None):
+    """``raw`` (n, 25, 25, 3) float64 / float32 HWC in [0, 1] (numpy or torch, host or device) ->
+    (n, 3, 25, 25) fp32 on the device, bit-equal to ``dataset.image_transform(x).float()`` per image
+    (dpt_image_normalize).  ``out``: write into this contiguous fp32 device tensor of n * 1875 floats."""
+    dev = device()
+    t = raw if isinstance(raw, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(raw))
+    code = _lib.IMAGE_RAW_DTYPES.get(str(t.dtype).replace("torch.", ""))
+    if code is None:
+        raise TypeError(f"normalize_images: expected float64 or float32 images in [0, 1], got {t.dtype}")
+    if t.dim() != 4 or tuple(t.shape[1:]) != (IMAGE_SIZE, IMAGE_SIZE, 3):
+        raise ValueError(f"normalize_images: raw {tuple(t.shape)} != (n, {IMAGE_SIZE}, {IMAGE_SIZE}, 3)")
+    t = t.to(dev).contiguous()
+    n = int(t.shape[0])
+    if out is None:
+        out = torch.empty((n, 3, IMAGE_SIZE, IMAGE_SIZE), dtype=torch.float32, device=dev)
+    if not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.numel() == n * 1875):
+        raise ValueError("normalize_images: `out` must be a contiguous fp32 device tensor of n * 1875 floats")
+    _lib.call("dpt_image_normalize", _p(t), code, n, _p(out), _stream())
+    return out
+
+
+class DeviceImageData:
+    """The image training set as dpt_image_data: dataset.py's ``ImageDataset`` with every image resident
+    on the device, normalised, in fp32.  Each trajectory's ``.npy`` stack is read once (and every
+    ``query_image``), the raw stacks are uploaded in chunks of at most ``chunk_bytes`` and normalised
+    there by dpt_image_normalize: no per-image host work.  The images take n (1 + horizon) 7,500 bytes.
+    ``from_arrays`` takes a collated batch dict whose images are normalised already."""
+
+    def __init__(self, image_dataset, chunk_bytes=256 << 20):
+        dev = device()
+        src = image_dataset.dataset
+        self._states(src, dev)
+        paths, trajs = src["context_filepaths"], image_dataset.trajs
+        if len(paths) != self.n or len(trajs) != self.n:
+            raise ValueError(f"dpt_hip.train: {len(paths)} image stacks for {self.n} samples")
+        try:
+            qi = torch.empty((self.n, 3, IMAGE_SIZE, IMAGE_SIZE), dtype=torch.float32, device=dev)
+            ci = torch.empty((self.n, self.horizon, 3, IMAGE_SIZE, IMAGE_SIZE), dtype=torch.float32, device=dev)
+        except torch.cuda.OutOfMemoryError as e:
+            raise MemoryError(f"DeviceImageData: {self.n} samples at horizon {self.horizon} need "
+                              f"{self.image_bytes} bytes of device memory for their images") from e
+        self.chunks = 0  # uploads made (one normalise launch each)
+        self._fill(qi, (np.asarray(t["query_image"])[None] for t in trajs), 1, chunk_bytes)
+        self._fill(ci, (np.load(p) for p in paths), self.horizon, chunk_bytes)
+        self._images(qi, ci)
+
+    @classmethod
+    def from_arrays(cls, arrays):
+        """The resident set of a batch dict as ``ImageDataset``'s items collate to (``query_images`` (n, 3,
+        25, 25) and ``context_images`` (n, H, 3, 25, 25) normalised already, plus IMAGE_DATA_KEYS)."""
+        self, dev = cls.__new__(cls), device()
+        self._states(arrays, dev)
+        self.chunks = 0
+        self._images(*(_dev(arrays[k], torch.float32, dev) for k in ("query_images", "context_images")))
+        return self
+
+    def _images(self, qi, ci):
+        want = {"query_images": (self.n, 3, IMAGE_SIZE, IMAGE_SIZE),
+                "context_images": (self.n, self.horizon, 3, IMAGE_SIZE, IMAGE_SIZE)}
+        for k, t in (("query_images", qi), ("context_images", ci)):
+            if tuple(t.shape) != want[k]:
+                raise ValueError(f"dpt_hip.train: {k} {tuple(t.shape)} != {want[k]}")
+            self.tensors[k] = t
+        self.struct = _lib.ImageData(self.n, self.horizon, IMAGE_SIZE,
+                                     *(_p(self.tensors[k]).value for k in IMAGE_DATA_KEYS + ("query_images",
+                                                                                            "context_images")))
+
+    def _states(self, src, dev):
+        self.tensors = {k: _dev(src[k], torch.float32, dev) for k in IMAGE_DATA_KEYS}
+        cs, ca = self.tensors["context_states"], self.tensors["context_actions"]
+        if cs.dim() != 3 or ca.dim() != 3:
+            raise ValueError("dpt_hip.train: expected context (n, H, .) arrays")
+        self.n, self.horizon, self.state_dim = int(cs.shape[0]), int(cs.shape[1]), int(cs.shape[2])
+        self.action_dim = int(ca.shape[2])
+        want = {"query_states": (self.n, self.state_dim), "context_actions": (self.n, self.horizon, self.action_dim),
+                "optimal_actions": (self.n, self.action_dim)}
+        for k, shape in want.items():
+            if tuple(self.tensors[k].shape) != shape:
+                raise ValueError(f"dpt_hip.train: {k} {tuple(self.tensors[k].shape)} != {shape}")
+        if self.tensors["context_rewards"].numel() != self.n * self.horizon:  # (n, H) or (n, H, 1)
+            raise ValueError("dpt_hip.train: context_rewards must hold one reward per transition")
+        self.image_bytes = self.n * (1 + self.horizon) * 4 * 3 * IMAGE_SIZE * IMAGE_SIZE
+
+    def _fill(self, out, stacks, per_item, chunk_bytes):
+        """normalise the items' raw stacks ((per_item, 25, 25, 3) each) into ``out`` in item order: one
+        upload and one launch per chunk of items of one dtype holding at most ``chunk_bytes``"""
+        flat = out.view(-1, 3, IMAGE_SIZE, IMAGE_SIZE)
+        pending, held, done = [], 0, 0
+
+        def flush():
+            nonlocal pending, held, done
+            if pending:
+                raw = np.concatenate(pending)
+                normalize_images(raw, flat[done:done + raw.shape[0]])
+                done += raw.shape[0]
+                self.chunks += 1
+            pending, held = [], 0
+        for stack in stacks:
+            if stack.shape != (per_item, IMAGE_SIZE, IMAGE_SIZE, 3):
+                raise ValueError(f"dpt_hip.train: image stack {stack.shape} != "
+                                 f"{(per_item, IMAGE_SIZE, IMAGE_SIZE, 3)}")
+            if pending and (stack.dtype != pending[0].dtype or held + stack.nbytes > chunk_bytes):
+                flush()
+            pending.append(stack)
+            held += stack.nbytes
+        flush()
+        if done != flat.shape[0]:
+            raise ValueError(f"dpt_hip.train: {done} images read for {flat.shape[0]} slots")
+
+    def __len__(self):
+        return self.n
+
+
+class ImageTrainer:
+    """The fused device training step of train_miniworld.py for a models.net.ImageTransformer.
+
+    Built like ``Trainer``: the fp32 master weights as two packed blobs (the trunk in the
+    dpt_train_desc layout with a zero emb_w / emb_b region, the front end in the front-blob layout),
+    AdamW's ``m`` and ``v`` for each, the step count, the workspace and a float64 loss accumulator, all
+    on the device.  ``step`` is one dpt_image_train_step: the batch gathered from the resident image
+    set, the image front end, the trunk, the summed cross-entropy, both backwards and the two AdamW
+    updates as a chain of launches on the current stream, with no host synchronisation; ``read_loss``
+    is the only call that waits for the device.  The module's own parameters are not touched until
+    ``sync_to_model``."""
+
+    def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8):
+        self.model = model
+        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
+        dev = device()
+        self.emb_numel = (2 * model.state_dim + model.action_dim + 1) * model.n_embd + model.n_embd
+        self.front_blob, self.blob = pack_image_params(image_param_list(model), self.emb_numel, dev)
+        self.m, self.v = torch.zeros_like(self.blob), torch.zeros_like(self.blob)
+        self.front_m, self.front_v = torch.zeros_like(self.front_blob), torch.zeros_like(self.front_blob)
+        self.steps = 0
+        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._ws = None
+        self._ws_batch = self._ws_window = 0  # the workspace grows to the largest batch seen
+        self._data = {}
+
+    def device_data(self, data, **kw):
+        """``data`` as DeviceImageData (an ImageDataset is converted once and kept)."""
+        if isinstance(data, DeviceImageData):
+            return data
+        dd = self._data.get(id(data))
+        if dd is None or dd[0] is not data:
+            dd = self._data[id(data)] = (data, DeviceImageData(data, **kw))
+        return dd[1]
+
+    def _desc(self, data, batch, seed):
+        m = self.model
+        if (data.state_dim, data.action_dim) != (m.state_dim, m.action_dim):
+            raise ValueError(f"dataset (sd {data.state_dim}, A {data.action_dim}) does not match the model "
+                             f"(sd {m.state_dim}, A {m.action_dim})")
+        p = 0.0
+        if m.dropout > 0:  # fresh masks per call; the reference's test loss runs in training mode too
+            p = float(m.dropout)
+            if seed is None:
+                from models.net import _dropout_seed
+                seed = _dropout_seed()
+        cap = max(batch, self._ws_batch)
+        d = desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, cap, 1 + data.horizon, dropout=p,
+                 seed=(int(seed) & (2 ** 64 - 1)) if p > 0 else 0)
+        if self._ws is None or cap > self._ws_batch or self._ws_window != d.window:
+            self._ws = torch.empty(_numel("dpt_image_train_step_workspace_numel", d), dtype=torch.float32,
+                                   device=self.blob.device)
+            self._ws_batch, self._ws_window = cap, d.window
+        return d
+
+    def step(self, data, index, perm=None, seed=None):
+        """One training step on the samples ``index`` (int64; ``perm`` (batch, horizon): each sample's
+        context permutation).  ``seed``: the Philox seed of this step's dropout masks (default: a fresh
+        one from the CUDA generator, as ``Trainer`` draws it).  Adds the batch's summed loss to the
+        accumulator."""
+        data = self.device_data(data)
+        idx, pm = _index_tensors(data, index, perm, self.blob.device)
+        d = self._desc(data, idx.numel(), seed)
+        self.steps += 1
+        args = _lib.AdamWArgs(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps)
+        try:
+            _lib.call("dpt_image_train_step", ctypes.byref(d), ctypes.byref(data.struct), _p(idx), _p(pm),
+                      idx.numel(), _p(self.blob), _p(self.m), _p(self.v), _p(self.front_blob), _p(self.front_m),
+                      _p(self.front_v), ctypes.byref(args), _p(self._ws), _p(self.loss), _stream())
+        except Exception:
+            self.steps -= 1  # rejected on the host before any launch
+            raise
+
+    def eval_loss(self, data, index, perm=None, seed=None):
+        """The test loss on the samples ``index`` (both forwards only, the model's dropout active); adds
+        the batch's summed loss to the accumulator."""
+        data = self.device_data(data)
+        idx, pm = _index_tensors(data, index, perm, self.blob.device)
+        d = self._desc(data, idx.numel(), seed)
+        _lib.call("dpt_image_train_eval_loss", ctypes.byref(d), ctypes.byref(data.struct), _p(idx), _p(pm),
+                  idx.numel(), _p(self.blob), _p(self.front_blob), _p(self._ws), _p(self.loss), _stream())
+
+    read_loss = Trainer.read_loss
+
+    def sync_to_model(self):
+        """Unpack both master blobs into the module's parameters (wte, which the model never reads, is
+        untouched)."""
+        params = image_param_list(self.model)
+        views = unpack_image_grads(self.front_blob, self.blob, self.emb_numel, [tuple(p.shape) for p in params])
+        with torch.no_grad():
+            for p, w in zip(params, views):
                 p.copy_(w)
         return self.model
 

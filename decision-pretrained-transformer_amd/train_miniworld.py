@@ -9,6 +9,14 @@ elsewhere (the Miniworld environment itself is out of scope).  The model is
 trunk's training kernels forward and backward (dpt_hip.train.ImageTransformerFunction), and
 ``torch.optim.AdamW`` steps the module's parameters.  ``--workers`` (default 16, the reference's
 ``num_workers``) sets the loader's worker processes; 0 loads in the main process.
+
+``--fused`` (opt-in) runs each batch as one fused device step instead (dpt_hip.train.ImageTrainer ->
+dpt_image_train_step): both datasets are read once into device-resident, device-normalised image sets
+(dpt_hip.train.DeviceImageData), the loader only yields sample indices (and the per-sample context
+permutations with ``--shuffle``) drawn from the CPU generator as the default path's loader draws them,
+AdamW runs on the device, and the loss is summed there and read once per epoch pass.  Checkpoints are
+the module's state_dict after ``ImageTrainer.sync_to_model()``.  Log lines, file names and the
+checkpoint schedule are the same.
 """
 import argparse
 import os
@@ -51,6 +59,16 @@ def _epoch_loss(model, loader, loss_fn, action_dim, horizon, optimizer=None):
     return total
 
 
+def _fused_epoch_loss(trainer, call, data, loader, horizon):
+    """``_epoch_loss`` on the fused path: one device step per (index[, perm]) batch, the summed loss read
+    once at the end -> the summed loss / horizon."""
+    for i, batch in enumerate(loader):
+        print(f"Batch {i} of {len(loader)}", end="\r")
+        index, perm = batch if isinstance(batch, (list, tuple)) else (batch, None)
+        call(data, index, perm)
+    return trainer.read_loss() / horizon
+
+
 def main(argv=None):
     os.makedirs("figs/loss", exist_ok=True)
     os.makedirs("trained_models", exist_ok=True)
@@ -60,7 +78,11 @@ def main(argv=None):
     common_args.add_model_args(parser)
     common_args.add_train_args(parser)
     parser.add_argument("--seed", type=int, default=0)
-    parser.add_argument("--workers", type=int, default=16, help="DataLoader worker processes (0: none)")
+    parser.add_argument("--workers", type=int, default=16,
+                        help="DataLoader worker processes (0: none); ignored with --fused, whose index loader "
+                             "runs in the main process")
+    parser.add_argument("--fused", action="store_true",
+                        help="one fused device step per batch on a device-resident image set (dpt_image_train_step)")
     args = vars(parser.parse_args(argv))
     print("Args: ", args)
 
@@ -107,8 +129,9 @@ def main(argv=None):
         with open(log_filename, "a") as f:
             print(string, file=f)
 
+    fused = args["fused"]
     params = {"batch_size": 64, "shuffle": True}
-    if args["workers"] > 0:
+    if args["workers"] > 0 and not fused:
         params.update({"num_workers": args["workers"], "prefetch_factor": 2, "persistent_workers": True,
                        "pin_memory": True, "worker_init_fn": worker_init_fn})
 
@@ -117,11 +140,20 @@ def main(argv=None):
     test_dataset = ImageDataset(paths_test, config, image_transform)
     printw("Done loading miniworld data")
 
-    train_loader = torch.utils.data.DataLoader(train_dataset, **params)
-    test_loader = torch.utils.data.DataLoader(test_dataset, **params)
+    if fused:
+        from dpt_hip.train import ImageTrainer
+        trainer = ImageTrainer(model, lr=lr, weight_decay=1e-4)
+        train_data, test_data = trainer.device_data(train_dataset), trainer.device_data(test_dataset)
+        train_loader = torch.utils.data.DataLoader(train_dataset.index_view(), **params)
+        test_loader = torch.utils.data.DataLoader(test_dataset.index_view(), **params)
+    else:
+        train_loader = torch.utils.data.DataLoader(train_dataset, **params)
+        test_loader = torch.utils.data.DataLoader(test_dataset, **params)
+        optimizer = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=1e-4)
+        loss_fn = torch.nn.CrossEntropyLoss(reduction="sum")
 
-    optimizer = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=1e-4)
-    loss_fn = torch.nn.CrossEntropyLoss(reduction="sum")
+    def state_dict():
+        return (trainer.sync_to_model() if fused else model).state_dict()
 
     test_loss, train_loss = [], []
     printw("Num train batches: " + str(len(train_loader)))
@@ -130,20 +162,26 @@ def main(argv=None):
     for epoch in range(args["num_epochs"]):
         printw(f"Epoch: {epoch + 1}")
         start_time = time.time()
-        with torch.no_grad():
-            total = _epoch_loss(model, test_loader, loss_fn, action_dim, horizon)
+        if fused:
+            total = _fused_epoch_loss(trainer, trainer.eval_loss, test_data, test_loader, horizon)
+        else:
+            with torch.no_grad():
+                total = _epoch_loss(model, test_loader, loss_fn, action_dim, horizon)
         test_loss.append(total / len(test_dataset))
         printw(f"\tTest loss: {test_loss[-1]}")
         printw(f"\tEval time: {time.time() - start_time}")
 
         start_time = time.time()
-        total = _epoch_loss(model, train_loader, loss_fn, action_dim, horizon, optimizer)
+        if fused:
+            total = _fused_epoch_loss(trainer, trainer.step, train_data, train_loader, horizon)
+        else:
+            total = _epoch_loss(model, train_loader, loss_fn, action_dim, horizon, optimizer)
         train_loss.append(total / len(train_dataset))
         printw(f"\tTrain loss: {train_loss[-1]}")
         printw(f"\tTrain time: {time.time() - start_time}")
 
         if (epoch + 1) % 50 == 0:
-            torch.save(model.state_dict(), f"trained_models/{filename}_epoch{epoch + 1}.pt")
+            torch.save(state_dict(), f"trained_models/{filename}_epoch{epoch + 1}.pt")
 
         if (epoch + 1) % 10 == 0:
             printw(f"Epoch: {epoch + 1}")
@@ -158,7 +196,7 @@ def main(argv=None):
             plt.savefig(f"figs/loss/{filename}_train_loss.png")
             plt.clf()
 
-    torch.save(model.state_dict(), f"trained_models/{filename}.pt")
+    torch.save(state_dict(), f"trained_models/{filename}.pt")
     print("Done.")
 
 

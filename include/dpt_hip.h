@@ -44,7 +44,10 @@ extern "C" {
  * and DPT_BANDIT_F32 in dpt_rollout_bandit_generic; the explorer/exploiter training step
  * (dpt_rollout_bandit_generic_env, DPT_STREAM_ENVACT, dpt_train_ce_rows, dpt_explore_weights,
  * dpt_explore_workspace_numel, dpt_explore_grad); the tuning key DPT_TUNE_YCACHE_BITS (dpt_rollout_bandit
- * caches its rows as 24-bit fixed point by default; no struct or signature changed) */
+ * caches its rows as 24-bit fixed point by default; no struct or signature changed); the image-conditioned
+ * DPT (dpt_image_front_*, dpt_train_*_embeds) and its training step (dpt_image_normalize,
+ * dpt_image_pack_batch, dpt_image_train_step_workspace_numel, dpt_image_train_step,
+ * dpt_image_train_eval_loss) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -736,6 +739,73 @@ int dpt_image_front_forward(const dpt_image_desc* desc_host, const float* front_
 int dpt_image_front_backward(const dpt_image_desc* desc_host, const float* front_blob, const float* images,
                              const float* feats, float* workspace, const float* dembeds, float* dfront_blob,
                              void* stream);
+
+/* ------------------------------------------------------------------ image training step
+ * One step of train.py:286-310 on the miniworld branch (and one batch of its test loss) for the
+ * image-conditioned DPT, as a chain of launches on one stream with no host synchronisation, no
+ * allocation, no side stream and no graph capture: pack the batch from a device-resident image set,
+ * dpt_image_front_forward, dpt_train_forward_embeds, dpt_train_ce_loss, dpt_train_backward_embeds,
+ * dpt_image_front_backward, then dpt_adamw_step on the trunk blob and on the front blob. */
+
+/* raw (n_images, 25, 25, 3) HWC in [0, 1] of float64 (dtype 0) or float32 (dtype 1), as the collected
+ * .npy stacks and query_image hold it -> out (n_images, 3, 25, 25) fp32 = (x - mean_c) / std_c with the
+ * ImageNet statistics of dataset.image_transform.  The subtraction and the IEEE division run in the
+ * input's dtype (the constants rounded to float32 first for float32 input) and the result is rounded to
+ * fp32 once: bit-equal to image_transform(x).float().  raw and out may sit at any element alignment.
+ * Fails before a launch on null pointers, an unknown dtype code or n_images < 0; n_images 0 launches
+ * nothing. */
+int dpt_image_normalize(const void* raw, int32_t dtype, int64_t n_images, float* out, void* stream);
+
+/* The whole image training set on the device in fp32 (dataset.py `ImageDataset`, images normalised). */
+typedef struct dpt_image_data {
+    int64_t n;                     /* samples */
+    int32_t horizon;               /* context transitions per sample */
+    int32_t image_size;            /* 25: the only size built */
+    const float* query_states;     /* (n, sd) */
+    const float* context_states;   /* (n, horizon, sd) */
+    const float* context_actions;  /* (n, horizon, A) */
+    const float* context_rewards;  /* (n, horizon) */
+    const float* optimal_actions;  /* (n, A) */
+    const float* query_images;     /* (n, 3, 25, 25) normalised */
+    const float* context_images;   /* (n, horizon, 3, 25, 25) normalised */
+} dpt_image_data;
+
+/* images (batch, 1 + horizon, 3, 25, 25), feats (batch, 1 + horizon, sd + A + 1) and targets (batch, A)
+ * for the samples index[b] (int64, any order, repeats allowed): row 0 of a sequence is the query (its
+ * image query_images[index[b]], its features [query_state | 0_A | 0]), row 1 + j the context transition
+ * perm[b][j] (j when perm is NULL) with its image and [state | action | reward]: the images and feats
+ * models/net.py:90-123 builds from ImageDataset's items.  Copies only: bit-exact.  An index outside
+ * [0, n) or a perm entry outside [0, horizon) reads nothing and packs zeros.  An image is 7500 bytes, so
+ * images start at every 4-byte alignment: the copy is correct at each and takes 16-byte accesses only
+ * where source and destination allow it.  desc: state_dim, action_dim and window (= 1 + horizon). */
+int dpt_image_pack_batch(const dpt_train_desc* desc_host, const dpt_image_data* data_host, const int64_t* index,
+                         const int64_t* perm, int32_t batch, float* images, float* feats, float* targets,
+                         void* stream);
+
+/* workspace floats of dpt_image_train_step / dpt_image_train_eval_loss for desc.batch sequences: the
+ * image and feature batch, targets, embeds, dembeds, preds, dpreds, the front and trunk workspaces,
+ * both gradient blobs and the per-sequence losses (every region rounded up to 4 floats) */
+int dpt_image_train_step_workspace_numel(const dpt_train_desc* desc_host, int64_t* numel_out_host);
+/* One step for the `batch` <= desc.batch samples of index (a smaller last batch reuses the workspace
+ * sized for desc.batch).  trunk_blob keeps the dpt_train_desc layout (its emb_w / emb_b region is never
+ * read, gets an exactly zero gradient and so stays zero), front_blob the front blob layout; each has its
+ * own m and v, all updated in place with the same args (AdamW is element-wise: two launches give the
+ * bits one would).  The dpt_image_desc is derived from desc: rows = batch * window, the same dropout and
+ * dropout_seed, so the encoder's masks and the trunk's come from one seed.  *loss_acc += the batch's
+ * summed loss over positions 1..window-1.  Host checks fail before any launch: null pointers, batch < 1
+ * or > desc.batch, desc flags != 0, desc.window != 1 + data->horizon, image_size != 25
+ * (DPT_EUNSUPPORTED), action_dim > 32 (DPT_EUNSUPPORTED), step < 1, a workspace or front blob that is
+ * not 16-byte aligned, equal trunk and front blobs. */
+int dpt_image_train_step(const dpt_train_desc* desc_host, const dpt_image_data* data_host, const int64_t* index,
+                         const int64_t* perm, int32_t batch, float* trunk_blob, float* trunk_m, float* trunk_v,
+                         float* front_blob, float* front_m, float* front_v, const dpt_adamw_args* args_host,
+                         float* workspace, double* loss_acc, void* stream);
+/* the test loss: pack -> both forwards with DPT_TRAIN_FORWARD_ONLY (every position) -> cross-entropy
+ * without a gradient.  desc.dropout stays active (the reference's test loss runs in training mode).
+ * Same workspace and host checks as dpt_image_train_step. */
+int dpt_image_train_eval_loss(const dpt_train_desc* desc_host, const dpt_image_data* data_host,
+                              const int64_t* index, const int64_t* perm, int32_t batch, const float* trunk_blob,
+                              const float* front_blob, float* workspace, double* loss_acc, void* stream);
 
 #ifdef __cplusplus
 }
