@@ -387,12 +387,13 @@ def rollin_bandit(means, cov, dirichlet, rand_index, u, g, var):
 
 
 def policy_action(policy, acts_ctx, rews_ctx, A, online=True, c=1.0, ts=None, ts_g=None, arms=None,
-                  first_u_idx=None):
+                  first_u_idx=None, sample=True):
     """One decision of a classical controller from its context (fp64 numpy, the reference's
     arithmetic).  acts_ctx (N, h) int, rews_ctx (N, h) float64.
 
     emp: ctrls/ctrl_bandit.py:89-118; ucb :348-380; lcb :286-314; thompson :184-236
-    (sample=True, posterior normals ts_g (N, A)); linucb :488-528 (first_u_idx (N) for h=0).
+    (sample=True, posterior normals ts_g (N, A); sample=False, :240-246: 100 posterior draws
+    ts_g (100, N, A), the first most frequent argmax); linucb :488-528 (first_u_idx (N) for h=0).
     """
     N, h = acts_ctx.shape
     if policy == "linucb":
@@ -434,6 +435,10 @@ def policy_action(policy, acts_ctx, rews_ctx, A, online=True, c=1.0, ts=None, ts
         mask = counts > 0
         means[mask] = new_mean[mask]
         variances[mask] = new_var[mask]
+        if not sample:  # the vote: each of the 100 draws names its best arm, the arm named most often wins
+            amax = np.argmax(means + np.sqrt(variances) * np.asarray(ts_g), axis=-1)  # (100, N)
+            freqs = (amax[:, :, None] == np.arange(A)).sum(0)  # (N, A) votes per arm
+            return np.argmax(freqs, axis=-1)  # ties: the lowest arm index, as np.argmax of the bincount
         return np.argmax(means + np.sqrt(variances) * ts_g, axis=-1)
     b_mean = b / np.maximum(1, counts)
     if policy in ("ucb", "lcb"):
@@ -452,7 +457,8 @@ def bandit_policy_rollout(policy, means, H, var, g, ctx_actions=None, ctx_reward
     g (H, N): reward normals, or uniforms with bernoulli=True (BanditEnv.transit's Binomial(1, mean),
     envs/bandit_env.py:56-64, as u < mean).  ctx_actions / ctx_rewards (N, C): a prefix context the
     controller sees before the first step (set_batch_numpy_vec, evals/eval_bandit.py:214-301).
-    kw: online, c, ts (dict std/prior_mean/prior_var), ts_g (H, N, A), arms, first_u_idx."""
+    kw: online, c, ts (dict std/prior_mean/prior_var), ts_g (H, N, A) -- with sample=False
+    (H, 100, N, A), row h handed to policy_action unchanged --, arms, first_u_idx."""
     means = np.asarray(means, np.float64)
     N, A = means.shape
     C = 0 if ctx_actions is None else np.asarray(ctx_actions).shape[1]

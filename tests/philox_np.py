@@ -7,11 +7,15 @@ MASK = np.uint64(0xFFFFFFFF)
 
 
 def philox(seed, step, task, stream):
+    """The four 32-bit words (uint64 arrays) of one block per key; step, task and stream broadcast
+    against each other (scalars or arrays)."""
     task = np.asarray(task, dtype=np.int64).astype(np.uint64)
-    step = np.uint64(step)
-    c0 = np.full(task.shape, step & MASK, dtype=np.uint64)
+    step = np.asarray(step).astype(np.uint64)
+    stream = np.asarray(stream).astype(np.uint64)
+    step, task, stream = (np.array(x) for x in np.broadcast_arrays(step, task, stream))
+    c0 = step & MASK
     c1 = task & MASK
-    c2 = np.full(task.shape, np.uint64(stream), dtype=np.uint64)
+    c2 = stream
     c3 = (task >> np.uint64(32)) ^ (step >> np.uint64(32))
     k0 = np.uint64(int(seed) & 0xFFFFFFFF)
     k1 = np.uint64((int(seed) >> 32) & 0xFFFFFFFF)
@@ -41,6 +45,13 @@ def normal(seed, step, task, stream):
     u1 = 1.0 - u53(x[0], x[1])
     u2 = u53(x[2], x[3])
     return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def randint(seed, step, task, stream, word, n):
+    """philox_randint of csrc/dpt_env.hip: the multiply-shift (word_w * n) >> 32 of one 32-bit
+    word of the block, an integer in [0, n); int64 array."""
+    w = philox(seed, step, task, stream)[word]
+    return ((w * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
 
 
 def dropout_keep(seed, p, site, shape):

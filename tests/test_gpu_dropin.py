@@ -659,7 +659,9 @@ def test_policy_wave_kernel_vs_oracle(A, H, C):
 
 def test_policy_lane_kernel_retired():
     """DPT_TUNE_POLICY_WAVE accepts only the wave kernel since round 6; dpt_policy_workspace_numel is
-    0 (the contexts live in LDS) and a null workspace is accepted."""
+    0 (the contexts live in LDS).  That a null workspace is accepted is shown where one is passed:
+    test_gpu_philox_paths.py test_null_workspace_is_accepted (dpt_hip.rollout_policy, used here,
+    always hands a buffer over)."""
     import ctypes
     import dpt_hip
     from dpt_hip import _lib
