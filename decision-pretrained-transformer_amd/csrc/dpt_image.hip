@@ -8,7 +8,9 @@
 //                 stay in LDS, the conv weights are staged once per workgroup.  conv2 (230 k of the
 //                 305 k multiply-adds of an image) is an implicit GEMM on v_mfma_f32_16x16x4_f32:
 //                 positions (100, in 7 tiles of 16) x K = (ci, ky, kx) = 144 x 16 output channels;
-//                 conv1 (27 taps) and the 1600 -> 8 product run on the VALU.
+//                 conv1 (27 taps) and the 1600 -> 8 product run on the VALU.  Its stages are the device
+//                 functions of dpt_image_enc.h, which the act step's fused front (dpt_imageact.hip)
+//                 calls too: one copy of the encoder's arithmetic.
 //   img_enc_bwd : conv1 recomputed from the image, dz2 from the fc gradient, then conv2's weight
 //                 gradient (co x (ci, ky, kx) over the positions) and data gradient ((y, x) x ci over
 //                 (co, ky, kx)) on the same MFMA form, conv1's weight gradient on the VALU.  The
@@ -23,44 +25,14 @@
 // which are the fc product's input and are > 0 exactly where the ReLU passed and the mask kept.
 #include <algorithm>
 
-#include "dpt_common.h"
+#include "dpt_image_enc.h"
 
 namespace dpt {
 
-constexpr int kImgThreads = 256;
 constexpr int kImgTileF = 4;   // images per workgroup, forward
 constexpr int kImgTileB = 8;   // images per workgroup, backward (one partial each)
-constexpr int kImgSize = 25, kImgPix = 3 * kImgSize * kImgSize;  // 1875 floats per image
-constexpr int kC1 = 12, kA1 = kC1 * kC1;   // conv1 output 16 x 12 x 12
-constexpr int kC2 = 10, kA2 = kC2 * kC2;   // conv2 output 16 x 10 x 10
-constexpr int kCh = 16, kEnc = 8, kFlat = kCh * kA2;  // 1600
-// LDS channel stride of the conv1 activations: the four k-groups of an MFMA operand read channels 4
-// apart, 4 * 148 = 16 (mod 32) banks apart (144 would put all four on the same banks); the 4 pad
-// floats per channel are zero (the weight gradient's padded columns read up to 2 past a channel)
-constexpr int kA1S = 148;
 constexpr int kDzW = 14, kDzS = kDzW * kDzW;  // dz2 with a zero border of 2: the data gradient reads (y - ky, x - kx)
 constexpr int kConvPart = 432 + 16 + 2304 + 16;  // one backward partial: conv1_w, conv1_b, conv2_w, conv2_b (blob order)
-
-// front blob offsets (dpt_hip.h order); F = 8 + sd + A + 1
-struct ImgBlob {
-    int64_t c1w, c1b, c2w, c2b, fcw, fcb, embw, embb, lng, lnb, total;
-    __host__ __device__ static ImgBlob make(int F, int E) {
-        ImgBlob b;
-        int64_t p = 0;
-        b.c1w = p; p += 432;
-        b.c1b = p; p += 16;
-        b.c2w = p; p += 2304;
-        b.c2b = p; p += 16;
-        b.fcw = p; p += (int64_t)kFlat * kEnc;
-        b.fcb = p; p += kEnc;
-        b.embw = p; p += (int64_t)F * E;
-        b.embb = p; p += E;
-        b.lng = p; p += E;
-        b.lnb = p; p += E;
-        b.total = p;
-        return b;
-    }
-};
 
 struct ImgDims {
     int rows, G, F, E, fwd_only;  // G = sd + A + 1 caller features per row, F = 8 + G
@@ -96,31 +68,6 @@ struct ImgWs {
     }
 };
 
-__device__ inline float img_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// a1[co][y][x] = relu(b[co] + sum_{ci, ky, kx} img[ci][2y + ky][2x + kx] w[co][ci][ky][kx]) into LDS (channel
-// stride kA1S); w1 = conv1_w then conv1_b (448 floats, LDS)
-__device__ inline void img_conv1(const float* __restrict__ w1, const float* __restrict__ img, float* __restrict__ a1) {
-    for (int o = threadIdx.x; o < kCh * kA1; o += kImgThreads) {
-        const int co = o / kA1, p = o % kA1, y = p / kC1, x = p % kC1;
-        const float* w = w1 + co * 27;
-        const float* in = img + (2 * y) * kImgSize + 2 * x;
-        float acc = w1[432 + co];
-#pragma unroll
-        for (int ci = 0; ci < 3; ++ci)
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx)
-                    acc = fmaf(in[ci * kImgSize * kImgSize + ky * kImgSize + kx], w[ci * 9 + ky * 3 + kx], acc);
-        a1[co * kA1S + p] = acc > 0.f ? acc : 0.f;
-    }
-}
-
 // ------------------------------------------------------------------------------ encoder forward
 // grid = ceil(rows / kImgTileF).  Writes tok[row] = [relu(fc) | feats[row]] and, when a2out is given
 // (a backward will follow), the dropped conv2 activations a2out[row][1600].
@@ -128,83 +75,26 @@ __global__ __launch_bounds__(kImgThreads) void img_enc_fwd(const float* __restri
                                                            const float* __restrict__ images,
                                                            const float* __restrict__ feats, ImgDims d,
                                                            float* __restrict__ a2out, float* __restrict__ tok) {
-    __shared__ float w1[448];            // conv1_w | conv1_b
-    __shared__ float w2t[144 * kCh];     // conv2_w as [k = ci 9 + ky 3 + kx][co]: a B operand read is 16 contiguous floats
-    __shared__ float b2[kCh];
-    __shared__ float img[kImgPix + 1];
-    __shared__ float a1[kCh * kA1S];
-    __shared__ float a2[kFlat];
-    __shared__ float red[kImgThreads / 64][kEnc];
+    __shared__ ImgEncLds s;
     const ImgBlob B = ImgBlob::make(d.F, d.E);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i16 = lane & 15, kq = lane >> 4;
-    for (int i = tid; i < 448; i += kImgThreads) w1[i] = blob[B.c1w + i];
-    for (int i = tid; i < 2304; i += kImgThreads) w2t[(i % 144) * kCh + i / 144] = blob[B.c2w + i];
-    if (tid < kCh) b2[tid] = blob[B.c2b + tid];
+    const int tid = threadIdx.x;
+    img_stage_weights(blob, B, s);
     const bool drop = d.drop.drop();
     const int row0 = blockIdx.x * kImgTileF;
     for (int im = 0; im < kImgTileF; ++im) {
         const int row = row0 + im;
         if (row >= d.rows) break;  // uniform over the workgroup
         __syncthreads();           // the staged weights; the previous image's readers are done
-        for (int i = tid; i < kImgPix; i += kImgThreads) img[i] = images[(int64_t)row * kImgPix + i];
+        for (int i = tid; i < kImgPix; i += kImgThreads) s.img[i] = images[(int64_t)row * kImgPix + i];
         __syncthreads();
-        img_conv1(w1, img, a1);
+        img_conv1(s.w1, s.img, s.a1);
         __syncthreads();
-        // conv2: z2[p][co] = sum_k a1patch[p][k] w2[k][co], k = (ci, ky, kx); lane (i16, kq) holds the
-        // k run kq 36 .. kq 36 + 35 = channels 4 kq .. 4 kq + 3 (A and B read the same k)
-        for (int mt = wave; mt < 7; mt += kImgThreads / 64) {
-            const int p = min(16 * mt + i16, kA2 - 1);  // positions past 99 compute a copy that is never stored
-            const float* ap = a1 + (4 * kq) * kA1S + (p / kC2) * kC1 + p % kC2;
-            const float* bp = w2t + (36 * kq) * kCh + i16;
-            floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < 36; ++s)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ap[(s / 9) * kA1S + ((s % 9) / 3) * kC1 + s % 3], bp[s * kCh],
-                                                           acc, 0, 0, 0);
-            // C layout: lane (co = i16, kq) holds positions 16 mt + 4 kq + r
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int pp = 16 * mt + 4 * kq + r;
-                if (pp >= kA2) continue;
-                float v = acc[r] + b2[i16];
-                v = v > 0.f ? v : 0.f;
-                if (drop) v *= tr_keep(d.drop, DPT_SITE_IMAGE_ENC, (int64_t)row * kFlat + i16 * kA2 + pp);
-                a2[i16 * kA2 + pp] = v;
-            }
-        }
+        img_conv2(s, d.drop, drop, row);
         __syncthreads();
-        // fc: thread-strided partial sums over the 1600 inputs, a wave tree, then the waves in order
-        float acc[kEnc];
-#pragma unroll
-        for (int j = 0; j < kEnc; ++j) acc[j] = 0.f;
-        for (int i = tid; i < kFlat; i += kImgThreads) {
-            const float v = a2[i];
-            if (a2out) a2out[(int64_t)row * kFlat + i] = v;
-            const floatx4* w = reinterpret_cast<const floatx4*>(blob + B.fcw + (int64_t)i * kEnc);
-            const floatx4 wa = w[0], wb = w[1];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                acc[j] = fmaf(v, wa[j], acc[j]);
-                acc[4 + j] = fmaf(v, wb[j], acc[4 + j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kEnc; ++j) acc[j] = img_wave_sum(acc[j]);
-        if (lane == 0) {
-#pragma unroll
-            for (int j = 0; j < kEnc; ++j) red[wave][j] = acc[j];
-        }
+        img_fc(blob, B, s, a2out ? a2out + (int64_t)row * kFlat : nullptr);
         __syncthreads();
-        for (int f = tid; f < d.F; f += kImgThreads) {
-            float v;
-            if (f < kEnc) {
-                v = ((red[0][f] + red[1][f]) + (red[2][f] + red[3][f])) + blob[B.fcb + f];
-                v = v > 0.f ? v : 0.f;
-            } else {
-                v = feats[(int64_t)row * d.G + (f - kEnc)];
-            }
-            tok[(int64_t)row * d.F + f] = v;
-        }
+        for (int f = tid; f < d.F; f += kImgThreads)
+            tok[(int64_t)row * d.F + f] = f < kEnc ? img_enc_out(blob, B, s, f) : feats[(int64_t)row * d.G + (f - kEnc)];
     }
 }
 

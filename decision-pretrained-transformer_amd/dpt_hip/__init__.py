@@ -504,3 +504,7 @@ def darkroom_memo():
 def set_prefill(on):
     """Windows up to DeviceModel.prefill_max_window() as one MFMA prefill (default) or position by position."""
     _lib.call("dpt_tuning_set", _lib.TUNE_PREFILL, int(bool(on)))
+
+
+# ----------------------------------------------------------------------------- image act step
+from .act import ImageActSession, obs_preprocess, obs_tables  # noqa: E402,F401

@@ -318,3 +318,33 @@ SIGNATURES["dpt_image_train_step"] = (_i32, [_train_desc_p, _image_data_p, _c_vo
                                              ctypes.POINTER(AdamWArgs), _c_void_p, _c_void_p, _c_void_p])
 SIGNATURES["dpt_image_train_eval_loss"] = (_i32, [_train_desc_p, _image_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
                                                   _c_void_p, _c_void_p, _c_void_p, _c_void_p])
+
+
+OBS_OUT = 25  # the resize's output side (DPT_OBS_OUT)
+OBS_BAND = 24  # weights kept per banded table row (DPT_OBS_BAND)
+OBS_MIN_SIDE, OBS_MAX_SIDE = 25, 128  # raw frame sides the resize is built for
+
+
+class ObsTables(ctypes.Structure):
+    """dpt_obs_tables: the anti-aliased resize to 25 x 25 as two banded tables (filled on the host,
+    uploaded once)."""
+    _fields_ = [("in_h", _i32), ("in_w", _i32), ("first_y", _i32 * OBS_OUT), ("count_y", _i32 * OBS_OUT),
+                ("first_x", _i32 * OBS_OUT), ("count_x", _i32 * OBS_OUT), ("wy", (_f64 * OBS_BAND) * OBS_OUT),
+                ("wx", (_f64 * OBS_BAND) * OBS_OUT)]
+
+
+class ImageActDesc(ctypes.Structure):
+    """dpt_image_act_desc: the act step of the image-conditioned DPT for ``batch`` envs."""
+    _fields_ = [("n_layer", _i32), ("n_embd", _i32), ("state_dim", _i32), ("action_dim", _i32),
+                ("n_positions", _i32), ("batch", _i32), ("max_context", _i32), ("image_size", _i32),
+                ("in_h", _i32), ("in_w", _i32), ("dropout", ctypes.c_float), ("reserved", _i32)]
+
+
+_act_desc_p = ctypes.POINTER(ImageActDesc)
+SIGNATURES["dpt_image_obs_tables"] = (_i32, [_i32, _i32, ctypes.POINTER(ObsTables)])
+SIGNATURES["dpt_image_obs_preprocess"] = (_i32, [_c_void_p, _i64, _i32, _i32, _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_image_act_workspace_numel"] = (_i32, [_act_desc_p, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_image_act_set_context"] = (_i32, [_act_desc_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                                  _c_void_p, _c_void_p])
+SIGNATURES["dpt_image_act_step"] = (_i32, [_act_desc_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                           _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p])

@@ -18,10 +18,11 @@ import torch  # noqa: E402
 
 import common_args  # noqa: E402
 from evals import eval_bandit, eval_darkroom, eval_linear_bandit  # noqa: E402
-from models.net import Transformer  # noqa: E402
+from models.net import ImageTransformer, Transformer  # noqa: E402
 from utils import (build_bandit_data_filename, build_bandit_model_filename,  # noqa: E402
                    build_darkroom_data_filename, build_darkroom_model_filename,
-                   build_linear_bandit_data_filename, build_linear_bandit_model_filename)
+                   build_linear_bandit_data_filename, build_linear_bandit_model_filename,
+                   build_miniworld_data_filename, build_miniworld_model_filename)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
@@ -72,12 +73,19 @@ def main(argv=None):
     elif envname.startswith("darkroom"):
         state_dim, action_dim = 2, 5
         filename = build_darkroom_model_filename(envname, model_config)
+    elif envname == "miniworld":
+        state_dim, action_dim = 2, 4
+        filename = build_miniworld_model_filename(envname, model_config)
     else:
-        raise NotImplementedError(f"{envname} (miniworld is out of scope)")
+        raise NotImplementedError(envname)
 
     config = {"horizon": H, "state_dim": state_dim, "action_dim": action_dim, "n_layer": args["layer"],
               "n_embd": args["embd"], "n_head": args["head"], "dropout": args["dropout"], "test": True}
-    model = Transformer(config).to(device)
+    if envname == "miniworld":
+        config.update({"image_size": 25})
+        model = ImageTransformer(config).to(device)
+    else:
+        model = Transformer(config).to(device)
     if args["checkpoint"] is not None:
         model_path = args["checkpoint"]
     elif epoch < 0:
@@ -96,6 +104,10 @@ def main(argv=None):
         dataset_config.update({"lin_d": lin_d, "var": var, "cov": cov})
         eval_filepath = build_linear_bandit_data_filename(envname, n_eval, dataset_config, mode=2)
         save_filename = f"{filename}_testcov{test_cov}_hor{horizon}.pkl"
+    elif envname == "miniworld":
+        dataset_config.update({"rollin_type": "uniform"})
+        eval_filepath = build_miniworld_data_filename(envname, 0, n_eval, dataset_config, mode=2)
+        save_filename = f"{filename}_hor{horizon}.pkl"
     else:
         dataset_config.update({"rollin_type": "uniform"})
         eval_filepath = build_darkroom_data_filename(envname, n_eval, dataset_config, mode=2)
@@ -130,6 +142,22 @@ def main(argv=None):
         plt.clf()
         eval_linear_bandit.offline_graph(eval_trajs, model, **cfg)
         plt.savefig(f"figs/{evals_filename}/graph/{save_filename}_graph.png")
+        plt.clf()
+    elif envname == "miniworld":
+        from evals import eval_miniworld  # the env factory needs gymnasium and miniworld (not part of this project)
+        video_dir = f"videos/{save_filename}/{evals_filename}"
+        cfg = {"Heps": 40, "horizon": horizon, "H": H, "n_eval": min(20, n_eval), "save_video": args["save_video"],
+               "filename_template": video_dir + "/{controller}_env{env_id}_ep{ep}_online.gif"}
+        if args["save_video"]:
+            os.makedirs(video_dir, exist_ok=True)
+        eval_miniworld.online(eval_trajs, model, **cfg)
+        plt.savefig(f"figs/{evals_filename}/online/{save_filename}.png")
+        plt.clf()
+        del cfg["Heps"], cfg["horizon"], cfg["H"]
+        cfg["n_eval"] = n_eval
+        cfg["filename_template"] = video_dir + "/{controller}_env{env_id}_offline.gif"
+        eval_miniworld.offline(eval_trajs, model, **cfg)
+        plt.savefig(f"figs/{evals_filename}/bar/{save_filename}_bar.png")
         plt.clf()
     else:
         cfg = {"Heps": 40, "horizon": horizon, "H": H, "n_eval": min(20, n_eval), "dim": dim,

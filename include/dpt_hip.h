@@ -47,7 +47,8 @@ extern "C" {
  * caches its rows as 24-bit fixed point by default; no struct or signature changed); the image-conditioned
  * DPT (dpt_image_front_*, dpt_train_*_embeds) and its training step (dpt_image_normalize,
  * dpt_image_pack_batch, dpt_image_train_step_workspace_numel, dpt_image_train_step,
- * dpt_image_train_eval_loss) */
+ * dpt_image_train_eval_loss); its act step (dpt_image_obs_tables, dpt_image_obs_preprocess,
+ * dpt_image_act_workspace_numel, dpt_image_act_set_context, dpt_image_act_step) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -806,6 +807,79 @@ int dpt_image_train_step(const dpt_train_desc* desc_host, const dpt_image_data* 
 int dpt_image_train_eval_loss(const dpt_train_desc* desc_host, const dpt_image_data* data_host,
                               const int64_t* index, const int64_t* perm, int32_t batch, const float* trunk_blob,
                               const float* front_blob, float* workspace, double* loss_acc, void* stream);
+
+/* ------------------------------------------------------------------ image act step (deployment)
+ * ctrls/ctrl_miniworld.py MiniworldTransformerController.act for B envs: the raw uint8 frame of each env is
+ * resized to 25 x 25 and normalised on the device, encoded, embedded and written into position 0 of
+ * that env's sequence; the context rows (fixed for an episode) are encoded once per episode.  ABI 8,
+ * additive.  The library still owns no memory. */
+
+/* skimage.transform.resize(frame_uint8, (25, 25, 3), anti_aliasing=True) (scikit-image 0.21) restated as a
+ * fixed separable linear map: frame / 255 -> ndimage.gaussian_filter(sigma = max(0, (n_in / 25 - 1) / 2)
+ * per axis, mode 'mirror', truncate 4) -> ndimage.zoom(order 1, mode 'mirror', grid_mode) -> clip (never
+ * acts: every weight is >= 0 and every row sums to 1).  R = Z G (25 x n_in) per axis, kept as banded
+ * rows: output o reads inputs first[o] .. first[o] + count[o] - 1 with weights w[o][0 .. count[o] - 1]
+ * (the rest of the row is 0: the kernels take eight taps a round and rely on it).  count <= DPT_OBS_BAND for every side in DPT_OBS_MIN_SIDE..DPT_OBS_MAX_SIDE. */
+#define DPT_OBS_OUT 25
+#define DPT_OBS_BAND 24
+#define DPT_OBS_MIN_SIDE 25
+#define DPT_OBS_MAX_SIDE 128
+typedef struct dpt_obs_tables {
+    int32_t in_h, in_w;
+    int32_t first_y[DPT_OBS_OUT], count_y[DPT_OBS_OUT];
+    int32_t first_x[DPT_OBS_OUT], count_x[DPT_OBS_OUT];
+    double wy[DPT_OBS_OUT][DPT_OBS_BAND];
+    double wx[DPT_OBS_OUT][DPT_OBS_BAND];
+} dpt_obs_tables;
+/* Host only, double precision, no device work: fills *tables_out_host for frames of in_h x in_w.  The
+ * caller uploads the struct once.  A side outside 25..128 is DPT_EUNSUPPORTED. */
+int dpt_image_obs_tables(int32_t in_h, int32_t in_w, dpt_obs_tables* tables_out_host);
+/* frames (n, in_h, in_w, 3) uint8 HWC, tables: the struct on the DEVICE -> out (n, 3, 25, 25) fp32 =
+ * float32(((R_y (x / 255) R_x^T) - mean_c) / std_c) with dpt_image_normalize's ImageNet statistics;
+ * accumulated in fp64 (the column pass, then the row pass, on the integer samples; then one IEEE division
+ * by 255, the subtraction and the division by std), rounded once on the store.  At 25 x 25 the tables are the identity and the result is bit-equal to dpt_image_normalize of
+ * float64(x) / 255.  One workgroup per frame.  A table the kernel reads is clamped to the frame, so a
+ * wrong one gives wrong values, never an access outside the frame.  Fails before a launch on null
+ * pointers, n < 0 and sides outside 25..128 (DPT_EUNSUPPORTED); n = 0 launches nothing. */
+int dpt_image_obs_preprocess(const uint8_t* frames, int64_t n, int32_t in_h, int32_t in_w,
+                             const dpt_obs_tables* tables_device, float* out, void* stream);
+
+typedef struct dpt_image_act_desc {
+    int32_t n_layer, n_embd, state_dim, action_dim, n_positions;
+    int32_t batch;       /* B envs */
+    int32_t max_context; /* the largest C the workspace is sized for */
+    int32_t image_size;  /* 25 */
+    int32_t in_h, in_w;  /* raw frame sides, 25..128 each */
+    float dropout;       /* must be 0: the act step is inference */
+    int32_t reserved;    /* 0 */
+} dpt_image_act_desc;
+/* floats: the front workspace and the embedded rows of batch * max_context context images, then the
+ * trunk's forward-only workspace at window 1 + max_context */
+int dpt_image_act_workspace_numel(const dpt_image_act_desc* desc_host, int64_t* numel_out_host);
+/* Once per episode: the batch * C context rows (images (B, C, 3, 25, 25) normalised, feats (B, C, sd + A
+ * + 1) = [state | action | reward]) through dpt_image_front_forward (DPT_TRAIN_FORWARD_ONLY) into rows
+ * 1..C of each sequence of embeds (B, 1 + C, E).  C = 0 is valid and launches nothing (images and feats
+ * may then be NULL). */
+int dpt_image_act_set_context(const dpt_image_act_desc* desc_host, int32_t C, const float* front_blob,
+                              const float* images, const float* feats, float* workspace, float* embeds,
+                              void* stream);
+/* One step, one chain on one stream with no host synchronisation and no allocation.  A fused front
+ * kernel, one workgroup per env: frames (B, in_h, in_w, 3) uint8 -> resize and normalise (arithmetic
+ * identical to dpt_image_obs_preprocess) -> obs_out (B, 3, 25, 25) -> conv1, conv2 (MFMA implicit GEMM),
+ * the 1600 -> 8 product (the device functions of dpt_image_front_forward's encoder: the same arithmetic
+ * order) -> embed_transition on [enc | query_states[b] | 0_A | 0] -> embed_ln -> embeds[b][0] (bit-equal
+ * to dpt_image_front_forward on (obs_out, feats) with 16-byte aligned embeds).  Then
+ * dpt_train_forward_embeds (DPT_TRAIN_FORWARD_ONLY | DPT_TRAIN_LAST_ONLY) at window 1 + C -> logits (B, A).
+ * Rows 1..C of embeds (dpt_image_act_set_context) are read, never written; no context image is read.
+ * Choose the action with dpt_select_action.  Host checks of the three entry points fail before any
+ * launch: null pointers, batch < 1, C < 0, C > max_context, 1 + C > n_positions, frame sides outside
+ * 25..128 (DPT_EUNSUPPORTED), image_size != 25 (DPT_EUNSUPPORTED), 8 + sd + A + 1 + n_embd above 6400
+ * (DPT_EUNSUPPORTED), dropout != 0, reserved != 0, a workspace, front blob or embeds that is not 16-byte
+ * aligned. */
+int dpt_image_act_step(const dpt_image_act_desc* desc_host, int32_t C, const float* trunk_blob,
+                       const float* front_blob, const uint8_t* frames, const dpt_obs_tables* tables_device,
+                       const float* query_states, float* workspace, float* embeds, float* obs_out, float* logits,
+                       void* stream);
 
 #ifdef __cplusplus
 }
