@@ -79,9 +79,10 @@ def _worst(got, ref):
     return worst, at
 
 
-def _assert_grads(label, got, ref, ref32=None):
+def _assert_grads(label, got, ref, ref32=None, bars=None):
     """print the worst errors (kernel and fp32 oracle, of max|g| per parameter), then hold every
-    parameter to BAR"""
+    parameter to BAR (or to its own entry of ``bars``, for callers whose models have bars of their
+    own: tests/sharp_models.py)"""
     worst, at = _worst(got, ref)
     line = f"train_grads {label}: kernel {worst:.3e} of max|g| ({at})"
     if ref32 is not None:
@@ -90,7 +91,7 @@ def _assert_grads(label, got, ref, ref32=None):
     print(line)
     for k, r in ref.items():
         e = np.abs(np.asarray(got[k], np.float64) - r).max()
-        assert e <= BAR * np.abs(r).max(), (label, k, e / np.abs(r).max())
+        assert e <= (BAR if bars is None else bars[k]) * np.abs(r).max(), (label, k, e / np.abs(r).max())
 
 
 def _oracle(w64, L, tok, dp, dtype):
@@ -102,22 +103,49 @@ def _oracle(w64, L, tok, dp, dtype):
     return preds.detach().numpy(), {k: v.grad.numpy() for k, v in P.items()}
 
 
-def _token_level(label, E, L, sd, B, T, last=False):
-    """The shared helper: dpt_train_forward / dpt_train_backward on random tokens and dpreds against
-    the float64 oracle.  Every parameter's gradient within BAR of its largest float64 entry, preds
-    within the logit bar, wpe's gradient rows at positions >= T exactly zero, a second forward +
-    backward bit-identical.  ``last``: DPT_TRAIN_LAST_LOSS with dpreds zero except at the last row
-    (preds are then compared at the last row, the only one that path writes)."""
-    from dpt_hip import train as tr
+def _token_inputs(E, L, sd, B, T, last=False, transform=None):
+    """the model (on the host), its float64 weights, the random tokens and dpreds of one _token_level
+    case; ``transform``: float64 weights -> the weights the case runs on (tests/sharp_models.py),
+    loaded into the module"""
     seed = 1000 * E + 10 * T + L + sd + B
     m, w64 = _model(E, L, sd, T, seed)
+    if transform is not None:
+        import sharp_models as SM
+        w64 = SM.as_f64(transform(w64))
+        SM.load_into(m, {k: v.astype(np.float32) for k, v in w64.items()})
     gen = torch.Generator().manual_seed(seed + 1)
     tok = torch.randn(B, T, 2 * sd + A + 1, generator=gen)
     dp = torch.randn(B, T, A, generator=gen)
     if last:
         dp[:, :-1] = 0
+    return m, w64, tok, dp
+
+
+def _token_level(label, E, L, sd, B, T, last=False, transform=None, level=None, perturb=None):
+    """The shared helper: dpt_train_forward / dpt_train_backward on random tokens and dpreds against
+    the float64 oracle.  Every parameter's gradient within BAR of its largest float64 entry, preds
+    within the logit bar, wpe's gradient rows at positions >= T exactly zero, a second forward +
+    backward bit-identical.  ``last``: DPT_TRAIN_LAST_LOSS with dpreds zero except at the last row
+    (preds are then compared at the last row, the only one that path writes).
+
+    ``transform`` / ``level``: the case runs on a model of tests/sharp_models.py; its attention
+    statistics are asserted first and its bars follow that module's rule (at ``sharp``, per parameter,
+    the larger of the project's bar and twice the fp32 oracle's error).  ``perturb``: applied to the
+    module after the oracle has run, so the kernels see other weights than the reference (the
+    bar-can-fail control).  Returns the printed figures."""
+    from dpt_hip import train as tr
+    m, w64, tok, dp = _token_inputs(E, L, sd, B, T, last, transform)
     preds64, g64 = _oracle(w64, L, tok, dp, torch.float64)
-    _, g32 = _oracle(w64, L, tok, dp, torch.float32)
+    preds32, g32 = _oracle(w64, L, tok, dp, torch.float32)
+    rows = slice(T - 1, T) if last else slice(None)
+    bars, preds_bar = None, 1e-5
+    if level is not None:
+        import sharp_models as SM
+        SM.assert_sharp(level, SM.token_stats(w64, L, tok.numpy()), label)
+        bars = {k: SM.bar(level, BAR, float(np.abs(g32[k] - r).max() / np.abs(r).max())) for k, r in g64.items()}
+        preds_bar = SM.bar(level, 1e-5, SM.rel_err(preds32[:, rows], preds64[:, rows]))
+    if perturb is not None:
+        perturb(m)
 
     m = m.cuda()
     params = tr.param_list(m)
@@ -129,14 +157,18 @@ def _token_level(label, E, L, sd, B, T, last=False):
         preds, ws = tr.forward(d, blob, tok_d)
         runs.append((preds, tr.backward(d, blob, tok_d, ws, dp_d)))
     got = {k: g.cpu().numpy() for k, g in zip(_names(m), tr.unpack_grads(runs[0][1], params))}
-    _assert_grads(label, got, g64, g32)
     p_got = runs[0][0].cpu().numpy()
-    rows = slice(T - 1, T) if last else slice(None)
-    assert (np.abs(p_got[:, rows] - preds64[:, rows]) <= 1e-5 * np.maximum(1, np.abs(preds64[:, rows]))).all(), \
+    p_err = np.abs(p_got[:, rows] - preds64[:, rows]) / np.maximum(1, np.abs(preds64[:, rows]))
+    if level is not None:
+        print(f"train_grads {label}: preds kernel {p_err.max():.3e}, fp32 oracle "
+              f"{np.abs((preds32[:, rows] - preds64[:, rows]) / np.maximum(1, np.abs(preds64[:, rows]))).max():.3e}")
+    _assert_grads(label, got, g64, g32, bars)
+    assert (np.abs(p_got[:, rows] - preds64[:, rows]) <= preds_bar * np.maximum(1, np.abs(preds64[:, rows]))).all(), \
         np.abs(p_got[:, rows] - preds64[:, rows]).max()
     assert m.n_positions > T and not got["transformer.wpe.weight"][T:].any()
     assert torch.equal(runs[0][1], runs[1][1])
     assert torch.equal(runs[0][0][:, rows], runs[1][0][:, rows])
+    return dict(grad=_worst(got, g64)[0], grad32=_worst(g32, g64)[0], preds=float(p_err.max()))
 
 
 # ----------------------------------------------------------------------------- 1. row kernels
