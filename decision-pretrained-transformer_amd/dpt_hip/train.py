@@ -12,23 +12,18 @@ holding the forward's saved activations is a torch tensor kept on the autograd c
 image front end (dpt_image_front_forward / _backward: conv encoder, embed_transition, embed_ln) chained
 into the trunk through dpt_train_forward_embeds / dpt_train_backward_embeds.
 
-``Trainer`` is the fused training step that train.py runs (dpt_train_step: batch packing from a
-device-resident dataset, forward, summed cross-entropy, backward, AdamW on the packed blob) with
-the master weights, the optimizer state and the loss accumulator kept on the device.
-
-``InteractiveTrainer`` is the fused on-policy bandit step that train_interactive.py runs
-(dpt_interactive_grad per chunk of envs: the y-cache rollout straight from the master blob, the
-window packed from its records, forward, last-position cross-entropy, backward; then dpt_adamw_step).
-
-``ExploreExploitTrainer`` is the fused two-model step that train_explorer_exploiter.py runs
-(dpt_explore_grad per chunk of envs: the explorer's rollout with the env stepped apart, one pack, the
-exploiter's and the explorer's forward / every-position cross-entropy / backward with the advantage
-weights in between; then dpt_adamw_step for each model).
-
-``DeviceImageData`` / ``ImageTrainer`` are the fused step that train_miniworld.py --fused runs
-(dpt_image_train_step: the batch gathered from a device-resident, device-normalised image set, the
-image front end, the trunk, summed cross-entropy, both backwards, dpt_adamw_step on the trunk blob and
-on the front blob).
+The four fused trainers keep everything on the device.  ``ModelState`` is one model's master blob with
+AdamW's ``m`` / ``v`` (and a gradient blob); ``_TrainerCore`` holds the hyper-parameters, the step count
+and the loss accumulator(s).  Under it, ``_DatasetTrainer`` is the one-call step on a device-resident
+dataset: ``Trainer`` (train.py; dpt_train_step on a ``DeviceData``: batch packing, forward, summed
+cross-entropy, backward, AdamW) and ``ImageTrainer`` (train_miniworld.py --fused; dpt_image_train_step on
+a ``DeviceImageData``: the image front end and the trunk, two blobs).  ``_BanditTrainer`` is the on-policy
+bandit episode, a gradient call per chunk of envs and then dpt_adamw_step per model:
+``InteractiveTrainer`` (train_interactive.py; dpt_interactive_grad: the y-cache rollout straight from the
+master blob, the window packed from its records, forward, last-position cross-entropy, backward) and
+``ExploreExploitTrainer`` (train_explorer_exploiter.py; dpt_explore_grad: the explorer's rollout with the
+env stepped apart, one pack, both models' forward / every-position cross-entropy / backward with the
+advantage weights in between).
 """
 import ctypes
 
@@ -400,96 +395,162 @@ def _index_tensors(data, index, perm, dev):
     return idx, pm
 
 
-class Trainer:
-    """The fused device training step of train.py:286-310 for a models.net.Transformer.
+class ModelState:
+    """One model's training state on the device: the fp32 master weights as one packed blob, AdamW's
+    ``m`` and ``v`` in the same layout and, for a trainer that calls dpt_adamw_step itself, the
+    gradient blob ``dblob``."""
 
-    Holds the fp32 master weights as one packed blob (include/dpt_hip.h layout), AdamW's ``m`` and
-    ``v`` in the same layout, the step count, the workspace and a float64 loss accumulator, all on
-    the device.  ``step`` is one dpt_train_step: batch packing, forward, summed cross-entropy,
-    backward and the AdamW update as a chain of launches on the current stream, with no host
-    synchronisation; ``read_loss`` is the only call that waits for the device.  The module's own
-    parameters are not touched until ``sync_to_model``."""
+    def __init__(self, blob, grad=False):
+        self.blob, self.m, self.v = blob, torch.zeros_like(blob), torch.zeros_like(blob)
+        self.dblob = torch.empty_like(blob) if grad else None
 
-    def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8):
-        self.model = model
+    def ptrs(self):
+        """(blob, m, v) for the fused entry points that run AdamW inside the library."""
+        return _p(self.blob), _p(self.m), _p(self.v)
+
+    def adamw(self, opt):
+        """One dpt_adamw_step from the gradient blob; ``opt``: the AdamWArgs (hyper-parameters, step number)."""
+        _lib.call("dpt_adamw_step", _p(self.blob), _p(self.dblob), _p(self.m), _p(self.v), self.blob.numel(),
+                  ctypes.byref(opt), _stream())
+
+    def copy_to(self, params, transposed, skip=0):
+        """Copy the master blob from float ``skip`` on into the module parameters ``params`` (blob order);
+        ``transposed``: the indices of the nn.Linear weights, [in][out] in the blob and [out][in] in torch."""
+        total = skip + sum(p.numel() for p in params)
+        if total != self.blob.numel():
+            raise ValueError(f"gradient blob {self.blob.numel()} != parameters {total}")
+        off = skip
+        with torch.no_grad():
+            for i, p in enumerate(params):
+                w = self.blob[off:off + p.numel()]
+                p.copy_(w.view(p.shape[1], p.shape[0]).t() if i in transposed else w.view(p.shape))
+                off += p.numel()
+
+
+def _sync(state, model):
+    """Unpack a Transformer's master blob into the module's parameters (wte, which the model never reads,
+    is untouched)."""
+    params = param_list(model)
+    state.copy_to(params, (0, len(params) - 2))
+    return model
+
+
+def _of(state, field):
+    """A trainer's public name for one tensor of its ModelState attribute ``state``."""
+    return property(lambda self: getattr(getattr(self, state), field))
+
+
+class _TrainerCore:
+    """What every fused trainer keeps besides its ModelStates: AdamW's hyper-parameters, the step count,
+    one float64 loss accumulator per loss (``loss``, on the device) and the workspace slot.  The trainers
+    launch on the current stream with no host synchronisation; ``read_loss`` (``read_losses``) is the only
+    call that waits for the device.  The modules' own parameters are not touched until ``sync_to_model``
+    (``sync_to_models``)."""
+
+    def __init__(self, lr, weight_decay, betas, eps, n_losses=1):
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
-        dev = device()
-        self.blob = pack_params(param_list(model), dev)
-        self.m = torch.zeros_like(self.blob)
-        self.v = torch.zeros_like(self.blob)
         self.steps = 0
-        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.loss = torch.zeros(n_losses, dtype=torch.float64, device=device())
         self._ws = None
+
+    def _adamw_args(self):
+        return _lib.AdamWArgs(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps)
+
+    def _read_losses(self):
+        vals = self.loss.tolist()  # the one device synchronisation
+        self.loss.zero_()
+        return vals
+
+    def read_loss(self):
+        """The accumulated loss sum (one device synchronisation), then reset to zero."""
+        return self._read_losses()[0]
+
+
+class _DatasetTrainer(_TrainerCore):
+    """The fused step on a device-resident dataset, one library call per batch: ``step`` packs or gathers
+    the batch, runs forward, summed cross-entropy, backward and AdamW; ``eval_loss`` runs the forwards and
+    the loss.  A subclass names its dataset wrapper and its three entry points and lists its ModelStates
+    in ``_states``: their (blob, m, v) go between the batch and the AdamW args, their blobs between the batch
+    and the workspace of ``eval_loss``."""
+    _DATA = _WS_NUMEL = _STEP = _EVAL = None
+
+    def __init__(self, model, lr, weight_decay, betas, eps):
+        super().__init__(lr, weight_decay, betas, eps)
+        self.model = model
         self._ws_batch = self._ws_window = 0  # the workspace grows to the largest batch seen
         self._data = {}
 
-    def device_data(self, data):
-        """``data`` as DeviceData (a Dataset / dict is converted once and kept)."""
-        if isinstance(data, DeviceData):
+    def device_data(self, data, **kw):
+        """``data`` as the device-resident set (a dataset / dict is converted once and kept)."""
+        if isinstance(data, self._DATA):
             return data
         dd = self._data.get(id(data))
         if dd is None or dd[0] is not data:
-            dd = self._data[id(data)] = (data, DeviceData(data))
+            dd = self._data[id(data)] = (data, self._DATA(data, **kw))
         return dd[1]
 
-    def _desc(self, data, batch):
+    def _desc(self, data, batch, seed=None):
         m = self.model
         if (data.state_dim, data.action_dim) != (m.state_dim, m.action_dim):
             raise ValueError(f"dataset (sd {data.state_dim}, A {data.action_dim}) does not match the model "
                              f"(sd {m.state_dim}, A {m.action_dim})")
-        p, seed = 0.0, 0
+        p = 0.0
         if m.dropout > 0:  # fresh masks per call; the reference's test loss runs in training mode too
-            from models.net import _dropout_seed
-            p, seed = float(m.dropout), _dropout_seed()
+            p = float(m.dropout)
+            if seed is None:
+                from models.net import _dropout_seed
+                seed = _dropout_seed()
         cap = max(batch, self._ws_batch)
         d = desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, cap, 1 + data.horizon, dropout=p,
-                 seed=seed)
+                 seed=(int(seed) & (2 ** 64 - 1)) if p > 0 else 0)
         if self._ws is None or cap > self._ws_batch or self._ws_window != d.window:
-            self._ws = torch.empty(_numel("dpt_train_step_workspace_numel", d), dtype=torch.float32,
-                                   device=self.blob.device)
+            self._ws = torch.empty(_numel(self._WS_NUMEL, d), dtype=torch.float32, device=self.loss.device)
             self._ws_batch, self._ws_window = cap, d.window
         return d
+
+    def _run(self, train, data, index, perm, seed=None):
+        data = self.device_data(data)
+        idx, pm = _index_tensors(data, index, perm, self.loss.device)
+        d = self._desc(data, idx.numel(), seed)
+        batch = (ctypes.byref(d), ctypes.byref(data.struct), _p(idx), _p(pm), idx.numel())
+        if not train:
+            return _lib.call(self._EVAL, *batch, *(_p(s.blob) for s in self._states), _p(self._ws), _p(self.loss),
+                             _stream())
+        self.steps += 1
+        try:
+            _lib.call(self._STEP, *batch, *(p for s in self._states for p in s.ptrs()),
+                      ctypes.byref(self._adamw_args()), _p(self._ws), _p(self.loss), _stream())
+        except Exception:
+            self.steps -= 1  # rejected on the host before any launch
+            raise
 
     def step(self, data, index, perm=None):
         """One training step on the samples ``index`` (int64; ``perm`` (batch, horizon): each
         sample's context permutation, dataset.py:84-89).  Adds the batch's summed loss to the
         accumulator."""
-        data = self.device_data(data)
-        idx, pm = _index_tensors(data, index, perm, self.blob.device)
-        d = self._desc(data, idx.numel())
-        self.steps += 1
-        args = _lib.AdamWArgs(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps)
-        try:
-            _lib.call("dpt_train_step", ctypes.byref(d), ctypes.byref(data.struct), _p(idx), _p(pm), idx.numel(),
-                      _p(self.blob), _p(self.m), _p(self.v), ctypes.byref(args), _p(self._ws), _p(self.loss),
-                      _stream())
-        except Exception:
-            self.steps -= 1  # rejected on the host before any launch
-            raise
+        self._run(True, data, index, perm)
 
     def eval_loss(self, data, index, perm=None):
         """The test loss of train.py:265-278 on the samples ``index`` (forward only, the model's
         dropout active); adds the batch's summed loss to the accumulator."""
-        data = self.device_data(data)
-        idx, pm = _index_tensors(data, index, perm, self.blob.device)
-        d = self._desc(data, idx.numel())
-        _lib.call("dpt_train_eval_loss", ctypes.byref(d), ctypes.byref(data.struct), _p(idx), _p(pm), idx.numel(),
-                  _p(self.blob), _p(self._ws), _p(self.loss), _stream())
+        self._run(False, data, index, perm)
 
-    def read_loss(self):
-        """The accumulated loss sum (one device synchronisation), then reset to zero."""
-        val = float(self.loss.item())
-        self.loss.zero_()
-        return val
+
+class Trainer(_DatasetTrainer):
+    """The fused device training step of train.py:286-310 for a models.net.Transformer (dpt_train_step on
+    a ``DeviceData``): one ModelState in the include/dpt_hip.h blob layout."""
+    _DATA, _WS_NUMEL, _STEP, _EVAL = DeviceData, "dpt_train_step_workspace_numel", "dpt_train_step", \
+        "dpt_train_eval_loss"
+    blob, m, v = _of("state", "blob"), _of("state", "m"), _of("state", "v")
+
+    def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8):
+        super().__init__(model, lr, weight_decay, betas, eps)
+        self.state = ModelState(pack_params(param_list(model), self.loss.device))
+        self._states = (self.state,)
 
     def sync_to_model(self):
-        """Unpack the master blob into the module's parameters (wte, which the model never reads,
-        is untouched)."""
-        params = param_list(self.model)
-        with torch.no_grad():
-            for p, w in zip(params, _unpack(self.blob, [p.shape for p in params], [p.dtype for p in params])):
-                p.copy_(w)
-        return self.model
+        """Unpack the master blob into the module's parameters."""
+        return _sync(self.state, self.model)
 
 
 IMAGE_DATA_KEYS = ("query_states", "context_states", "context_actions", "context_rewards", "optimal_actions")
@@ -608,98 +669,39 @@ class DeviceImageData:
         return self.n
 
 
-class ImageTrainer:
-    """The fused device training step of train_miniworld.py for a models.net.ImageTransformer.
-
-    Built like ``Trainer``: the fp32 master weights as two packed blobs (the trunk in the
-    dpt_train_desc layout with a zero emb_w / emb_b region, the front end in the front-blob layout),
-    AdamW's ``m`` and ``v`` for each, the step count, the workspace and a float64 loss accumulator, all
-    on the device.  ``step`` is one dpt_image_train_step: the batch gathered from the resident image
-    set, the image front end, the trunk, the summed cross-entropy, both backwards and the two AdamW
-    updates as a chain of launches on the current stream, with no host synchronisation; ``read_loss``
-    is the only call that waits for the device.  The module's own parameters are not touched until
-    ``sync_to_model``."""
+class ImageTrainer(_DatasetTrainer):
+    """The fused device training step of train_miniworld.py for a models.net.ImageTransformer
+    (dpt_image_train_step on a ``DeviceImageData``: the image front end, the trunk, the summed
+    cross-entropy, both backwards and the two AdamW updates).  Two ModelStates: the trunk in the
+    dpt_train_desc layout with a zero emb_w / emb_b region of ``emb_numel`` floats, the front end in the
+    front-blob layout."""
+    _DATA, _WS_NUMEL, _STEP, _EVAL = DeviceImageData, "dpt_image_train_step_workspace_numel", \
+        "dpt_image_train_step", "dpt_image_train_eval_loss"
+    blob, m, v = _of("trunk", "blob"), _of("trunk", "m"), _of("trunk", "v")
+    front_blob, front_m, front_v = _of("front", "blob"), _of("front", "m"), _of("front", "v")
 
     def __init__(self, model, lr, weight_decay=1e-4, betas=(0.9, 0.999), eps=1e-8):
-        self.model = model
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
-        dev = device()
+        super().__init__(model, lr, weight_decay, betas, eps)
         self.emb_numel = (2 * model.state_dim + model.action_dim + 1) * model.n_embd + model.n_embd
-        self.front_blob, self.blob = pack_image_params(image_param_list(model), self.emb_numel, dev)
-        self.m, self.v = torch.zeros_like(self.blob), torch.zeros_like(self.blob)
-        self.front_m, self.front_v = torch.zeros_like(self.front_blob), torch.zeros_like(self.front_blob)
-        self.steps = 0
-        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
-        self._ws = None
-        self._ws_batch = self._ws_window = 0  # the workspace grows to the largest batch seen
-        self._data = {}
-
-    def device_data(self, data, **kw):
-        """``data`` as DeviceImageData (an ImageDataset is converted once and kept)."""
-        if isinstance(data, DeviceImageData):
-            return data
-        dd = self._data.get(id(data))
-        if dd is None or dd[0] is not data:
-            dd = self._data[id(data)] = (data, DeviceImageData(data, **kw))
-        return dd[1]
-
-    def _desc(self, data, batch, seed):
-        m = self.model
-        if (data.state_dim, data.action_dim) != (m.state_dim, m.action_dim):
-            raise ValueError(f"dataset (sd {data.state_dim}, A {data.action_dim}) does not match the model "
-                             f"(sd {m.state_dim}, A {m.action_dim})")
-        p = 0.0
-        if m.dropout > 0:  # fresh masks per call; the reference's test loss runs in training mode too
-            p = float(m.dropout)
-            if seed is None:
-                from models.net import _dropout_seed
-                seed = _dropout_seed()
-        cap = max(batch, self._ws_batch)
-        d = desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, cap, 1 + data.horizon, dropout=p,
-                 seed=(int(seed) & (2 ** 64 - 1)) if p > 0 else 0)
-        if self._ws is None or cap > self._ws_batch or self._ws_window != d.window:
-            self._ws = torch.empty(_numel("dpt_image_train_step_workspace_numel", d), dtype=torch.float32,
-                                   device=self.blob.device)
-            self._ws_batch, self._ws_window = cap, d.window
-        return d
+        front, trunk = pack_image_params(image_param_list(model), self.emb_numel, self.loss.device)
+        self._states = self.trunk, self.front = ModelState(trunk), ModelState(front)
 
     def step(self, data, index, perm=None, seed=None):
-        """One training step on the samples ``index`` (int64; ``perm`` (batch, horizon): each sample's
-        context permutation).  ``seed``: the Philox seed of this step's dropout masks (default: a fresh
-        one from the CUDA generator, as ``Trainer`` draws it).  Adds the batch's summed loss to the
-        accumulator."""
-        data = self.device_data(data)
-        idx, pm = _index_tensors(data, index, perm, self.blob.device)
-        d = self._desc(data, idx.numel(), seed)
-        self.steps += 1
-        args = _lib.AdamWArgs(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps)
-        try:
-            _lib.call("dpt_image_train_step", ctypes.byref(d), ctypes.byref(data.struct), _p(idx), _p(pm),
-                      idx.numel(), _p(self.blob), _p(self.m), _p(self.v), _p(self.front_blob), _p(self.front_m),
-                      _p(self.front_v), ctypes.byref(args), _p(self._ws), _p(self.loss), _stream())
-        except Exception:
-            self.steps -= 1  # rejected on the host before any launch
-            raise
+        """``_DatasetTrainer.step``; ``seed``: the Philox seed of this step's dropout masks (default: a
+        fresh one from the CUDA generator)."""
+        self._run(True, data, index, perm, seed)
 
     def eval_loss(self, data, index, perm=None, seed=None):
         """The test loss on the samples ``index`` (both forwards only, the model's dropout active); adds
         the batch's summed loss to the accumulator."""
-        data = self.device_data(data)
-        idx, pm = _index_tensors(data, index, perm, self.blob.device)
-        d = self._desc(data, idx.numel(), seed)
-        _lib.call("dpt_image_train_eval_loss", ctypes.byref(d), ctypes.byref(data.struct), _p(idx), _p(pm),
-                  idx.numel(), _p(self.blob), _p(self.front_blob), _p(self._ws), _p(self.loss), _stream())
-
-    read_loss = Trainer.read_loss
+        self._run(False, data, index, perm, seed)
 
     def sync_to_model(self):
         """Unpack both master blobs into the module's parameters (wte, which the model never reads, is
         untouched)."""
         params = image_param_list(self.model)
-        views = unpack_image_grads(self.front_blob, self.blob, self.emb_numel, [tuple(p.shape) for p in params])
-        with torch.no_grad():
-            for p, w in zip(params, views):
-                p.copy_(w)
+        self.front.copy_to(params[:N_FRONT], (4, 6))  # fc / embed_transition weights
+        self.trunk.copy_to(params[N_FRONT:], (len(params) - N_FRONT - 2,), skip=self.emb_numel)
         return self.model
 
 
@@ -769,56 +771,97 @@ def chunk_plan(n, chunk):
     return [(off, min(size, n - off)) for off in range(0, n, size)]
 
 
-class InteractiveTrainer:
-    """The fused interactive (on-policy) bandit step of train_interactive.py:92-143 for a
-    models.net.Transformer with state_dim 1 and no dropout.
+class _BanditTrainer(_TrainerCore):
+    """The fused on-policy bandit episode for models.net.Transformers with state_dim 1 and no dropout: one
+    ModelState with a gradient blob per model (``_states``, in the order AdamW updates them).  ``step``
+    validates the episode (``_episode``), then ``_train`` runs the subclass's gradient entry point once per
+    chunk of envs -- the K - 1 sampled rollout steps from the master blob, the window packed from the
+    records, forward, cross-entropy, backward; chunk 0 writes the gradient blobs, later chunks add to them
+    in chunk order -- and one dpt_adamw_step per model."""
+    _WS_NUMEL = None
 
-    Built like ``Trainer``: the fp32 master blob, AdamW's ``m`` and ``v``, the gradient blob, the
-    step count, the workspace and a float64 loss accumulator live on the device.  ``step`` runs one
-    dpt_interactive_grad per chunk of envs (K - 1 sampled rollout steps from the blob, the window
-    packed from the records, forward, last-position cross-entropy scaled by 1 / N, backward), the
-    chunks' gradients added in chunk order, then one dpt_adamw_step -- all on the current stream
-    with no host synchronisation; ``read_loss`` is the only call that waits for the device."""
-
-    def __init__(self, model, lr, weight_decay=1e-4, chunk=0, betas=(0.9, 0.999), eps=1e-8, full_width=False):
-        # full_width: the last block for every row instead of the last one (DPT_INTERACTIVE_FULL_WIDTH; A/B runs)
-        self.full_width = bool(full_width)
-        if model.state_dim != 1:
-            raise ValueError(f"InteractiveTrainer: state_dim={model.state_dim} (bandits have state_dim 1)")
-        if model.dropout != 0:
-            raise ValueError("InteractiveTrainer: dropout must be 0 (the cached decode has no dropout masks)")
+    def __init__(self, models, lr, weight_decay, chunk, betas, eps, n_losses=1):
+        name = type(self).__name__
+        for m in models:
+            if m.state_dim != 1:
+                raise ValueError(f"{name}: state_dim={m.state_dim} (bandits have state_dim 1)")
+            if m.dropout != 0:
+                raise ValueError(f"{name}: dropout must be 0 (the cached decode has no dropout masks)")
         if int(chunk) < 0:
-            raise ValueError(f"InteractiveTrainer: chunk={chunk}")
-        self.model, self.chunk = model, int(chunk)
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
-        dev = device()
-        self.blob = pack_params(param_list(model), dev)
-        self.m = torch.zeros_like(self.blob)
-        self.v = torch.zeros_like(self.blob)
-        self.dblob = torch.empty_like(self.blob)
-        self.steps = 0
-        self.loss = torch.zeros(1, dtype=torch.float64, device=dev)
-        self._ws = None
+            raise ValueError(f"{name}: chunk={chunk}")
+        super().__init__(lr, weight_decay, betas, eps, n_losses)
+        self.chunk = int(chunk)
+        self._states = tuple(ModelState(pack_params(param_list(m), self.loss.device), grad=True) for m in models)
+        m = models[0]
+        self._d = desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, 1, 1)
         self._ws_shape = (0, 0)  # (chunk envs, K) the workspace was sized for
 
-    def _desc(self):
-        m = self.model
-        return desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, 1, 1)
-
-    def _workspace(self, d, n, K):
+    def _workspace(self, n, K):
         if self._ws is not None and self._ws_shape == (n, K):
             return self._ws
         need = ctypes.c_int64()
-        _lib.call("dpt_interactive_workspace_numel", ctypes.byref(d), n, K, ctypes.byref(need))
+        _lib.call(self._WS_NUMEL, ctypes.byref(self._d), n, K, ctypes.byref(need))
         self._ws = None  # release the old one first
         try:
-            self._ws = torch.empty(need.value, dtype=torch.float32, device=self.blob.device)
+            self._ws = torch.empty(need.value, dtype=torch.float32, device=self.loss.device)
         except torch.cuda.OutOfMemoryError as e:
-            raise MemoryError(f"InteractiveTrainer: one chunk of {n} envs at K={K} needs a workspace of "
+            raise MemoryError(f"{type(self).__name__}: one chunk of {n} envs at K={K} needs a workspace of "
                               f"{4 * need.value} bytes; pass a smaller `chunk` (now {self.chunk}; 0 = all envs at "
                               f"once)") from e
         self._ws_shape = (n, K)
         return self._ws
+
+    def _episode(self, means, K, bandit_type, targets, seed, **draws):
+        """The episode's inputs on the device, validated: (means (N, A) float64, the DPT_BANDIT_* code,
+        targets (N) int64, the 64-bit seed, the injected ``draws`` in the order given -- each None or a
+        (K - 1, N) tensor, int32 for ``env_actions`` and float64 otherwise)."""
+        from . import next_seed
+        dev, A = self.loss.device, self._d.action_dim
+        means_d = _dev(means, torch.float64, dev)
+        if means_d.dim() != 2 or means_d.shape[1] != A or means_d.shape[0] < 1:
+            raise ValueError(f"means {tuple(means_d.shape)} != (N >= 1, action_dim {A})")
+        N = int(means_d.shape[0])
+        code = {"uniform": _lib.BANDIT_GAUSSIAN, "bernoulli": _lib.BANDIT_BERNOULLI}.get(bandit_type, bandit_type)
+        tg = means_d.argmax(dim=1) if targets is None else _dev(targets, torch.int64, dev).reshape(-1)
+        if tg.numel() != N:
+            raise ValueError(f"targets {tg.numel()} != envs {N}")
+        out = []
+        for name, x in draws.items():
+            x = None if x is None else _dev(x, torch.int32 if name == "env_actions" else torch.float64, dev)
+            if x is not None and tuple(x.shape) != (K - 1, N):
+                raise ValueError(f"{name} {tuple(x.shape)} != (K - 1 = {K - 1}, N = {N})")
+            out.append(x)
+        return means_d, int(code), tg, (next_seed() if seed is None else int(seed)) & (2 ** 64 - 1), out
+
+    def _train(self, N, K, draws, grad):
+        """``grad(ws, i, off, n, *chunk draws)`` for chunk ``i`` = envs off..off+n, then the AdamW updates."""
+        plan = chunk_plan(N, self.chunk)
+        ws = self._workspace(plan[0][1], K)
+        for i, (off, n) in enumerate(plan):
+            # rows off..off+n of the (N, K-1) records are one contiguous block; the draws' columns are copied
+            grad(ws, i, off, n, *(None if x is None else x[:, off:off + n].contiguous() for x in draws))
+        self.steps += 1
+        opt = self._adamw_args()
+        for s in self._states:
+            s.adamw(opt)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()  # a c_void_p field of an args struct
+
+
+class InteractiveTrainer(_BanditTrainer):
+    """The fused interactive (on-policy) bandit step of train_interactive.py:92-143: one
+    dpt_interactive_grad per chunk of envs with the last-position cross-entropy scaled by 1 / N, then one
+    dpt_adamw_step."""
+    _WS_NUMEL = "dpt_interactive_workspace_numel"
+    blob, m, v, dblob = _of("state", "blob"), _of("state", "m"), _of("state", "v"), _of("state", "dblob")
+
+    def __init__(self, model, lr, weight_decay=1e-4, chunk=0, betas=(0.9, 0.999), eps=1e-8, full_width=False):
+        # full_width: the last block for every row instead of the last one (DPT_INTERACTIVE_FULL_WIDTH; A/B runs)
+        self.full_width = bool(full_width)
+        super().__init__((model,), lr, weight_decay, chunk, betas, eps)
+        self.model, (self.state,) = model, self._states
 
     def step(self, means, K, var, bandit_type, uniforms=None, noise=None, seed=None, targets=None):
         """One episode: ``means`` (N, A) arm means, ``K`` the window (K - 1 rolled-out steps),
@@ -827,62 +870,39 @@ class InteractiveTrainer:
         (K - 1, N) inject the selection uniforms / reward draws; otherwise Philox keyed by ``seed``
         (default: dpt_hip.next_seed()) and the env's global index.  Adds the step's mean loss to the
         accumulator and returns the recorded (actions (N, K-1) int32, rewards (N, K-1) float64)."""
-        from . import next_seed
-        dev = self.blob.device
         K = int(K)
-        means_d = _dev(means, torch.float64, dev)
-        if means_d.dim() != 2 or means_d.shape[1] != self.model.action_dim or means_d.shape[0] < 1:
-            raise ValueError(f"means {tuple(means_d.shape)} != (N >= 1, action_dim {self.model.action_dim})")
-        N = int(means_d.shape[0])
-        code = {"uniform": _lib.BANDIT_GAUSSIAN, "bernoulli": _lib.BANDIT_BERNOULLI}.get(bandit_type, bandit_type)
-        tg = means_d.argmax(dim=1) if targets is None else _dev(targets, torch.int64, dev).reshape(-1)
-        if tg.numel() != N:
-            raise ValueError(f"targets {tg.numel()} != envs {N}")
-        draws = []
-        for name, x in (("uniforms", uniforms), ("noise", noise)):
-            x = None if x is None else _dev(x, torch.float64, dev)
-            if x is not None and tuple(x.shape) != (K - 1, N):
-                raise ValueError(f"{name} {tuple(x.shape)} != (K - 1 = {K - 1}, N = {N})")
-            draws.append(x)
-        seed = (next_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
-        actions = torch.empty((N, max(K - 1, 0)), dtype=torch.int32, device=dev)
-        rewards = torch.empty((N, max(K - 1, 0)), dtype=torch.float64, device=dev)
-        d = self._desc()
-        plan = chunk_plan(N, self.chunk)
-        ws = self._workspace(d, plan[0][1], K)
+        means_d, code, tg, seed, draws = self._episode(means, K, bandit_type, targets, seed, uniforms=uniforms,
+                                                       noise=noise)
+        N, s = int(means_d.shape[0]), self.state
+        actions = torch.empty((N, max(K - 1, 0)), dtype=torch.int32, device=means_d.device)
+        rewards = torch.empty((N, max(K - 1, 0)), dtype=torch.float64, device=means_d.device)
         base_flags = _lib.INTERACTIVE_FULL_WIDTH if self.full_width else 0
-        for i, (off, n) in enumerate(plan):
-            # rows off..off+n of the (N, K-1) records are one contiguous block; the draws' columns are copied
-            u_c, g_c = (None if x is None else x[:, off:off + n].contiguous() for x in draws)
+
+        def grad(ws, i, off, n, u_c, g_c):
             args = _lib.InteractiveArgs(
-                n, K, int(code), base_flags | (_lib.INTERACTIVE_ACCUMULATE if i > 0 else 0), off, float(var), 1.0 / N, seed, 0, _p(means_d[off:off + n]).value,
-                _p(tg[off:off + n]).value, None if u_c is None else _p(u_c).value,
-                None if g_c is None else _p(g_c).value, _p(actions[off:off + n]).value,
-                _p(rewards[off:off + n]).value, _p(ws).value, _p(self.dblob).value, _p(self.loss).value)
-            _lib.call("dpt_interactive_grad", ctypes.byref(d), _p(self.blob), ctypes.byref(args), _stream())
-        self.steps += 1
-        opt = _lib.AdamWArgs(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps)
-        _lib.call("dpt_adamw_step", _p(self.blob), _p(self.dblob), _p(self.m), _p(self.v), self.blob.numel(),
-                  ctypes.byref(opt), _stream())
+                n, K, code, base_flags | (_lib.INTERACTIVE_ACCUMULATE if i > 0 else 0), off, float(var), 1.0 / N,
+                seed, 0, _ptr(means_d[off:off + n]), _ptr(tg[off:off + n]), _ptr(u_c), _ptr(g_c),
+                _ptr(actions[off:off + n]), _ptr(rewards[off:off + n]), _ptr(ws), _ptr(s.dblob), _ptr(self.loss))
+            _lib.call("dpt_interactive_grad", ctypes.byref(self._d), _p(s.blob), ctypes.byref(args), _stream())
+        self._train(N, K, draws, grad)
         return actions, rewards
 
-    read_loss = Trainer.read_loss
-    sync_to_model = Trainer.sync_to_model
+    def sync_to_model(self):
+        """Unpack the master blob into the module's parameters."""
+        return _sync(self.state, self.model)
 
 
-class ExploreExploitTrainer:
+class ExploreExploitTrainer(_BanditTrainer):
     """The fused explorer/exploiter bandit step of train_explorer_exploiter.py:102-192 for two
-    models.net.Transformers of one config (state_dim 1, no dropout).
-
-    Built like ``InteractiveTrainer``, twice over: each model's fp32 master blob, AdamW ``m`` / ``v``
-    and gradient blob, one step count, ONE workspace shared by the two models and two float64 loss
-    accumulators live on the device.  ``step`` runs one dpt_explore_grad per chunk of envs (the
-    explorer's K - 1 sampled rollout steps with the env stepped by a separate arm, the window packed
-    once, the exploiter's forward / every-position cross-entropy / backward, the advantage weights
-    from its row losses, the explorer's forward / weighted cross-entropy / backward), the chunks'
-    gradients added in chunk order, then one dpt_adamw_step per model -- all on the current stream
-    with no host synchronisation; ``read_losses`` is the only call that waits for the device.  The
-    advantages use the exploiter's weights from before its update."""
+    models.net.Transformers of one config: ONE workspace shared by the two models, two loss accumulators.
+    One dpt_explore_grad per chunk of envs (the explorer's K - 1 sampled rollout steps with the env stepped
+    by a separate arm, the window packed once, the exploiter's forward / every-position cross-entropy /
+    backward, the advantage weights from its row losses, the explorer's forward / weighted cross-entropy /
+    backward), then one dpt_adamw_step per model, the exploiter's first.  The advantages use the
+    exploiter's weights from before its update."""
+    _WS_NUMEL = "dpt_explore_workspace_numel"
+    explorer_blob, explorer_dblob = _of("explorer_state", "blob"), _of("explorer_state", "dblob")
+    exploiter_blob, exploiter_dblob = _of("exploiter_state", "blob"), _of("exploiter_state", "dblob")
 
     def __init__(self, explorer, exploiter, lr, weight_decay=1e-4, chunk=0, betas=(0.9, 0.999), eps=1e-8):
         if explorer is exploiter:
@@ -890,46 +910,10 @@ class ExploreExploitTrainer:
         cfg = [(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions) for m in (explorer, exploiter)]
         if cfg[0] != cfg[1]:
             raise ValueError(f"ExploreExploitTrainer: the two models differ in shape ({cfg[0]} != {cfg[1]})")
-        for m in (explorer, exploiter):
-            if m.state_dim != 1:
-                raise ValueError(f"ExploreExploitTrainer: state_dim={m.state_dim} (bandits have state_dim 1)")
-            if m.dropout != 0:
-                raise ValueError("ExploreExploitTrainer: dropout must be 0 (the cached decode has no dropout masks)")
-        if int(chunk) < 0:
-            raise ValueError(f"ExploreExploitTrainer: chunk={chunk}")
-        self.explorer, self.exploiter, self.chunk = explorer, exploiter, int(chunk)
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
-        dev = device()
-        # per model: [blob, m, v, dblob]
-        self.explorer_blob, self.exploiter_blob = (pack_params(param_list(m), dev) for m in (explorer, exploiter))
-        self._state = {}
-        for name, blob in (("explorer", self.explorer_blob), ("exploiter", self.exploiter_blob)):
-            self._state[name] = (blob, torch.zeros_like(blob), torch.zeros_like(blob), torch.empty_like(blob))
-        self.explorer_dblob, self.exploiter_dblob = self._state["explorer"][3], self._state["exploiter"][3]
-        self.steps = 0
-        self.loss_explorer = torch.zeros(1, dtype=torch.float64, device=dev)
-        self.loss_exploiter = torch.zeros(1, dtype=torch.float64, device=dev)
-        self._ws = None
-        self._ws_shape = (0, 0)  # (chunk envs, K) the workspace was sized for
-
-    def _desc(self):
-        m = self.explorer
-        return desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, 1, 1)
-
-    def _workspace(self, d, n, K):
-        if self._ws is not None and self._ws_shape == (n, K):
-            return self._ws
-        need = ctypes.c_int64()
-        _lib.call("dpt_explore_workspace_numel", ctypes.byref(d), n, K, ctypes.byref(need))
-        self._ws = None  # release the old one first
-        try:
-            self._ws = torch.empty(need.value, dtype=torch.float32, device=self.explorer_blob.device)
-        except torch.cuda.OutOfMemoryError as e:
-            raise MemoryError(f"ExploreExploitTrainer: one chunk of {n} envs at K={K} needs a workspace of "
-                              f"{4 * need.value} bytes; pass a smaller `chunk` (now {self.chunk}; 0 = all envs at "
-                              f"once)") from e
-        self._ws_shape = (n, K)
-        return self._ws
+        super().__init__((exploiter, explorer), lr, weight_decay, chunk, betas, eps, n_losses=2)
+        self.explorer, self.exploiter = explorer, exploiter
+        self.exploiter_state, self.explorer_state = self._states
+        self.loss_explorer, self.loss_exploiter = self.loss[:1], self.loss[1:]
 
     def step(self, means, K, var, bandit_type, beta, uniforms=None, noise=None, env_actions=None, seed=None,
              targets=None):
@@ -941,65 +925,33 @@ class ExploreExploitTrainer:
         ``seed`` (default: dpt_hip.next_seed()) and the env's global index.  Adds the step's two mean
         losses to the accumulators and returns the records (context actions (N, K-1) int32, env
         actions (N, K-1) int32, rewards (N, K-1) float64)."""
-        from . import next_seed
-        dev = self.explorer_blob.device
         K, beta = int(K), float(beta)
-        A = self.explorer.action_dim
         if K < 2:
             raise ValueError(f"ExploreExploitTrainer: K={K} (the explorer's loss is a mean over K - 1 positions: "
                              f"K >= 2)")
-        means_d = _dev(means, torch.float64, dev)
-        if means_d.dim() != 2 or means_d.shape[1] != A or means_d.shape[0] < 1:
-            raise ValueError(f"means {tuple(means_d.shape)} != (N >= 1, action_dim {A})")
-        N = int(means_d.shape[0])
-        code = {"uniform": _lib.BANDIT_GAUSSIAN, "bernoulli": _lib.BANDIT_BERNOULLI}.get(bandit_type, bandit_type)
-        tg = means_d.argmax(dim=1) if targets is None else _dev(targets, torch.int64, dev).reshape(-1)
-        if tg.numel() != N:
-            raise ValueError(f"targets {tg.numel()} != envs {N}")
-        draws = []
-        for name, x, dt in (("uniforms", uniforms, torch.float64), ("noise", noise, torch.float64),
-                            ("env_actions", env_actions, torch.int32)):
-            x = None if x is None else _dev(x, dt, dev)
-            if x is not None and tuple(x.shape) != (K - 1, N):
-                raise ValueError(f"{name} {tuple(x.shape)} != (K - 1 = {K - 1}, N = {N})")
-            draws.append(x)
-        seed = (next_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
-        actions = torch.empty((N, K - 1), dtype=torch.int32, device=dev)
-        env_acts = torch.empty((N, K - 1), dtype=torch.int32, device=dev)
-        rewards = torch.empty((N, K - 1), dtype=torch.float64, device=dev)
-        d = self._desc()
-        plan = chunk_plan(N, self.chunk)
-        ws = self._workspace(d, plan[0][1], K)
-        for i, (off, n) in enumerate(plan):
-            # rows off..off+n of the (N, K-1) records are one contiguous block; the draws' columns are copied
-            u_c, g_c, e_c = (None if x is None else x[:, off:off + n].contiguous() for x in draws)
+        means_d, code, tg, seed, draws = self._episode(means, K, bandit_type, targets, seed, uniforms=uniforms,
+                                                       noise=noise, env_actions=env_actions)
+        N, ex, xp = int(means_d.shape[0]), self.explorer_state, self.exploiter_state
+        actions = torch.empty((N, K - 1), dtype=torch.int32, device=means_d.device)
+        env_acts = torch.empty((N, K - 1), dtype=torch.int32, device=means_d.device)
+        rewards = torch.empty((N, K - 1), dtype=torch.float64, device=means_d.device)
+
+        def grad(ws, i, off, n, u_c, g_c, e_c):
             args = _lib.ExploreArgs(
-                n, K, int(code), _lib.EXPLORE_ACCUMULATE if i > 0 else 0, off, float(var), beta, 1.0 / (N * K),
-                1.0 / (N * (K - 1)), seed, 0, _p(means_d[off:off + n]).value, _p(tg[off:off + n]).value,
-                *(None if x is None else _p(x).value for x in (u_c, g_c, e_c)), _p(actions[off:off + n]).value,
-                _p(env_acts[off:off + n]).value, _p(rewards[off:off + n]).value, _p(ws).value,
-                _p(self.explorer_dblob).value, _p(self.exploiter_dblob).value, _p(self.loss_explorer).value,
-                _p(self.loss_exploiter).value)
-            _lib.call("dpt_explore_grad", ctypes.byref(d), _p(self.explorer_blob), _p(self.exploiter_blob),
-                      ctypes.byref(args), _stream())
-        self.steps += 1
-        opt = _lib.AdamWArgs(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.steps)
-        for blob, m, v, dblob in (self._state["exploiter"], self._state["explorer"]):
-            _lib.call("dpt_adamw_step", _p(blob), _p(dblob), _p(m), _p(v), blob.numel(), ctypes.byref(opt), _stream())
+                n, K, code, _lib.EXPLORE_ACCUMULATE if i > 0 else 0, off, float(var), beta, 1.0 / (N * K),
+                1.0 / (N * (K - 1)), seed, 0, _ptr(means_d[off:off + n]), _ptr(tg[off:off + n]), _ptr(u_c),
+                _ptr(g_c), _ptr(e_c), _ptr(actions[off:off + n]), _ptr(env_acts[off:off + n]),
+                _ptr(rewards[off:off + n]), _ptr(ws), _ptr(ex.dblob), _ptr(xp.dblob), _ptr(self.loss_explorer),
+                _ptr(self.loss_exploiter))
+            _lib.call("dpt_explore_grad", ctypes.byref(self._d), _p(ex.blob), _p(xp.blob), ctypes.byref(args),
+                      _stream())
+        self._train(N, K, draws, grad)
         return actions, env_acts, rewards
 
     def read_losses(self):
         """The accumulated (explorer, exploiter) loss sums (one device synchronisation), then reset."""
-        both = torch.cat([self.loss_explorer, self.loss_exploiter]).cpu()
-        self.loss_explorer.zero_()
-        self.loss_exploiter.zero_()
-        return float(both[0]), float(both[1])
+        return tuple(self._read_losses())
 
     def sync_to_models(self):
         """Unpack the two master blobs into the modules' parameters (wte is untouched)."""
-        with torch.no_grad():
-            for model, blob in ((self.explorer, self.explorer_blob), (self.exploiter, self.exploiter_blob)):
-                params = param_list(model)
-                for p, w in zip(params, _unpack(blob, [p.shape for p in params], [p.dtype for p in params])):
-                    p.copy_(w)
-        return self.explorer, self.exploiter
+        return _sync(self.explorer_state, self.explorer), _sync(self.exploiter_state, self.exploiter)

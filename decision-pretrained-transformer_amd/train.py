@@ -11,34 +11,20 @@ there and read once per epoch.  Checkpoints are the module's state_dict after
 """
 import argparse
 import os
-import random
 import time
 
-import matplotlib
+import torch
 
-matplotlib.use("Agg")
-import matplotlib.pyplot as plt  # noqa: E402
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import common_args  # noqa: E402
-from dataset import Dataset  # noqa: E402
-from dpt_hip.train import Trainer  # noqa: E402
-from models.net import Transformer  # noqa: E402
-from utils import (build_bandit_data_filename, build_bandit_model_filename,  # noqa: E402
+import common_args
+from dataset import Dataset
+from dpt_hip.train import Trainer
+from models.net import Transformer
+from train_common import LossLog, run_epoch, set_seeds
+from utils import (build_bandit_data_filename, build_bandit_model_filename,
                    build_darkroom_data_filename, build_darkroom_model_filename,
                    build_linear_bandit_data_filename, build_linear_bandit_model_filename)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
-
-
-def _run_epoch(trainer, call, data, loader):
-    """One pass over ``loader`` (index batches, or (index, perm) batches) -> the summed loss."""
-    for i, batch in enumerate(loader):
-        print(f"Batch {i} of {len(loader)}", end="\r")
-        index, perm = batch if isinstance(batch, (list, tuple)) else (batch, None)
-        call(data, index, perm)
-    return trainer.read_loss()
 
 
 def main(argv=None):
@@ -58,13 +44,7 @@ def main(argv=None):
     lr, shuffle, seed = args["lr"], args["shuffle"], args["seed"]
     var, cov, lin_d = args["var"], args["cov"], args["lin_d"]
 
-    tmp_seed = 0 if seed == -1 else seed
-    torch.manual_seed(tmp_seed)
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed(tmp_seed)
-        torch.cuda.manual_seed_all(tmp_seed)
-    np.random.seed(tmp_seed)
-    random.seed(tmp_seed)
+    set_seeds(0 if seed == -1 else seed)
 
     if shuffle and env == "linear_bandit":
         raise Exception("Are you sure you want to shuffle on the linear bandit? Data collected from an adaptive "
@@ -99,15 +79,7 @@ def main(argv=None):
               "test": False, "store_gpu": True}
     model = Transformer(config).to(device)
 
-    log_filename = f"figs/loss/{filename}_logs.txt"
-    with open(log_filename, "w"):
-        pass
-
-    def printw(string):
-        """print, and append the same line to the log file"""
-        print(string)
-        with open(log_filename, "a") as f:
-            print(string, file=f)
+    printw = LossLog(filename)
 
     train_dataset = Dataset(path_train, config)
     test_dataset = Dataset(path_test, config)
@@ -125,13 +97,13 @@ def main(argv=None):
     for epoch in range(args["num_epochs"]):
         printw(f"Epoch: {epoch + 1}")
         start_time = time.time()
-        total = _run_epoch(trainer, trainer.eval_loss, test_data, test_loader)
+        total = run_epoch(trainer, trainer.eval_loss, test_data, test_loader)
         test_loss.append(total / horizon / len(test_dataset))
         printw(f"\tTest loss: {test_loss[-1]}")
         printw(f"\tEval time: {time.time() - start_time}")
 
         start_time = time.time()
-        total = _run_epoch(trainer, trainer.step, train_data, train_loader)
+        total = run_epoch(trainer, trainer.step, train_data, train_loader)
         train_loss.append(total / horizon / len(train_dataset))
         printw(f"\tTrain loss: {train_loss[-1]}")
         printw(f"\tTrain time: {time.time() - start_time}")
@@ -139,18 +111,7 @@ def main(argv=None):
         if (epoch + 1) % 50 == 0 or (env == "linear_bandit" and (epoch + 1) % 10 == 0):
             torch.save(trainer.sync_to_model().state_dict(), f"trained_models/{filename}_epoch{epoch + 1}.pt")
 
-        if (epoch + 1) % 10 == 0:
-            printw(f"Epoch: {epoch + 1}")
-            printw(f"Test Loss:        {test_loss[-1]}")
-            printw(f"Train Loss:       {train_loss[-1]}")
-            printw("\n")
-
-            plt.yscale("log")
-            plt.plot(train_loss[1:], label="Train Loss")
-            plt.plot(test_loss[1:], label="Test Loss")
-            plt.legend()
-            plt.savefig(f"figs/loss/{filename}_train_loss.png")
-            plt.clf()
+        printw.report(epoch, test_loss, train_loss)
 
     torch.save(trainer.sync_to_model().state_dict(), f"trained_models/{filename}.pt")
     print("Done.")

@@ -13,10 +13,8 @@ and ``interactive_step_plain`` runs instead: a per-step loop on the module with 
 """
 import argparse
 import os
-import random
 import time
 
-import numpy as np
 import torch
 
 import common_args
@@ -24,17 +22,7 @@ import dpt_hip
 from dpt_hip.train import InteractiveTrainer
 from envs.gpu_bandit_env import GPUBanditEnv
 from models.net import Transformer
-
-
-def set_seeds(seed):
-    torch.manual_seed(seed)
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed(seed)
-        torch.cuda.manual_seed_all(seed)
-    torch.backends.cudnn.deterministic = True
-    torch.backends.cudnn.benchmark = False
-    np.random.seed(seed)
-    random.seed(seed)
+from train_common import set_seeds
 
 
 def build_bandit_env(dim, n_envs, horizon, var, env_name, device=None):
@@ -98,7 +86,7 @@ def main(argv=None):
     K = args["K"] if args["K"] > 0 else args["H"]
     dim, var, n_envs = args["dim"], args["var"], args["envs"]
     num_epochs, episodes = args["num_epochs"], args["episodes_per_epoch"]
-    set_seeds(0 if args["seed"] == -1 else args["seed"])
+    set_seeds(0 if args["seed"] == -1 else args["seed"], cudnn=True)
 
     device = dpt_hip.device()
     config = {"horizon": K, "state_dim": 1, "action_dim": dim, "n_layer": args["layer"], "n_embd": args["embd"],

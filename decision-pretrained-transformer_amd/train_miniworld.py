@@ -20,20 +20,16 @@ checkpoint schedule are the same.
 """
 import argparse
 import os
-import random
 import time
 
-import matplotlib
+import numpy as np
+import torch
 
-matplotlib.use("Agg")
-import matplotlib.pyplot as plt  # noqa: E402
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import common_args  # noqa: E402
-from dataset import ImageDataset, image_transform  # noqa: E402
-from models.net import ImageTransformer  # noqa: E402
-from utils import build_miniworld_data_filename, build_miniworld_model_filename, worker_init_fn  # noqa: E402
+import common_args
+from dataset import ImageDataset, image_transform
+from models.net import ImageTransformer
+from train_common import LossLog, run_epoch, set_seeds
+from utils import build_miniworld_data_filename, build_miniworld_model_filename, worker_init_fn
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
@@ -57,16 +53,6 @@ def _epoch_loss(model, loader, loss_fn, action_dim, horizon, optimizer=None):
             optimizer.step()
         total += loss.item() / horizon
     return total
-
-
-def _fused_epoch_loss(trainer, call, data, loader, horizon):
-    """``_epoch_loss`` on the fused path: one device step per (index[, perm]) batch, the summed loss read
-    once at the end -> the summed loss / horizon."""
-    for i, batch in enumerate(loader):
-        print(f"Batch {i} of {len(loader)}", end="\r")
-        index, perm = batch if isinstance(batch, (list, tuple)) else (batch, None)
-        call(data, index, perm)
-    return trainer.read_loss() / horizon
 
 
 def main(argv=None):
@@ -93,13 +79,7 @@ def main(argv=None):
     lr, shuffle, seed = args["lr"], args["shuffle"], args["seed"]
     state_dim, action_dim = 2, 4  # the direction vector (no position), four actions
 
-    tmp_seed = 0 if seed == -1 else seed
-    torch.manual_seed(tmp_seed)
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed(tmp_seed)
-        torch.cuda.manual_seed_all(tmp_seed)
-    np.random.seed(tmp_seed)
-    random.seed(tmp_seed)
+    set_seeds(0 if seed == -1 else seed)
 
     dataset_config = {"n_hists": args["hists"], "n_samples": args["samples"], "horizon": horizon, "dim": dim,
                       "rollin_type": "uniform"}
@@ -119,15 +99,7 @@ def main(argv=None):
               "test": False, "store_gpu": False, "image_size": 25}
     model = ImageTransformer(config).to(device)
 
-    log_filename = f"figs/loss/{filename}_logs.txt"
-    with open(log_filename, "w"):
-        pass
-
-    def printw(string):
-        """print, and append the same line to the log file"""
-        print(string)
-        with open(log_filename, "a") as f:
-            print(string, file=f)
+    printw = LossLog(filename)
 
     fused = args["fused"]
     params = {"batch_size": 64, "shuffle": True}
@@ -163,7 +135,7 @@ def main(argv=None):
         printw(f"Epoch: {epoch + 1}")
         start_time = time.time()
         if fused:
-            total = _fused_epoch_loss(trainer, trainer.eval_loss, test_data, test_loader, horizon)
+            total = run_epoch(trainer, trainer.eval_loss, test_data, test_loader) / horizon
         else:
             with torch.no_grad():
                 total = _epoch_loss(model, test_loader, loss_fn, action_dim, horizon)
@@ -173,7 +145,7 @@ def main(argv=None):
 
         start_time = time.time()
         if fused:
-            total = _fused_epoch_loss(trainer, trainer.step, train_data, train_loader, horizon)
+            total = run_epoch(trainer, trainer.step, train_data, train_loader) / horizon
         else:
             total = _epoch_loss(model, train_loader, loss_fn, action_dim, horizon, optimizer)
         train_loss.append(total / len(train_dataset))
@@ -183,18 +155,7 @@ def main(argv=None):
         if (epoch + 1) % 50 == 0:
             torch.save(state_dict(), f"trained_models/{filename}_epoch{epoch + 1}.pt")
 
-        if (epoch + 1) % 10 == 0:
-            printw(f"Epoch: {epoch + 1}")
-            printw(f"Test Loss:        {test_loss[-1]}")
-            printw(f"Train Loss:       {train_loss[-1]}")
-            printw("\n")
-
-            plt.yscale("log")
-            plt.plot(train_loss[1:], label="Train Loss")
-            plt.plot(test_loss[1:], label="Test Loss")
-            plt.legend()
-            plt.savefig(f"figs/loss/{filename}_train_loss.png")
-            plt.clf()
+        printw.report(epoch, test_loss, train_loss)
 
     torch.save(state_dict(), f"trained_models/{filename}.pt")
     print("Done.")

@@ -3,13 +3,16 @@ each in its own process (python scripts/ab_lib.py libA.so libB.so ...; rounds al
 An argument libX.so:<bytes> runs libX.so with dpt_hip.set_cache_budget(<bytes>); a suffix +b0 / +nob0
 runs it with dpt_hip.set_block0_mfma(True / False); +nows / +nomemo run DarkRoom without the
 layer-0 workspace / the logits memo (suffixes in that order: lib.so+nows+nomemo); a last suffix
-+y32 / +y24 sets dpt_hip.set_ycache_bits (a build without that key fails when it is set).
++y32 / +y24 sets dpt_hip.set_ycache_bits (a build without that key fails when it is set).  libX.so@<file>.py
+(before any other suffix) loads that file in place of dpt_hip/train.py: an A/B of the Python layer on one library.
 Env: AB_H, AB_N, AB_A, AB_TILE, AB_ROUNDS.
 AB_WL=train: the training entry points instead (trunk forward / backward, generic rollout, the three
-cross-entropies, the fused steps): one sha1 per case over the raw bytes of every output, then the ms
-per dpt_train_step at the shapes of scripts/train_timing.py (AB_STEPS steps between device events).
-The parent exits 1 when two libraries' digests differ and writes digests.txt / ab.json to AB_OUT
-(default profiles/train_refactor)."""
+cross-entropies, the fused steps and the four trainer classes over several steps): one sha1 per case over
+the raw bytes of every output, then the ms per dpt_train_step at the shapes of scripts/train_timing.py
+(AB_STEPS steps between device events) and the host microseconds to enqueue one step of each trainer.
+The parent exits 1 when two arguments' digests differ and writes digests.txt / ab.json to AB_OUT
+(default profiles/train_refactor); ab.json's ``over_margin`` lists the figures whose median exceeds the
+first argument's by more than the first argument's own max - min."""
 import ctypes
 import hashlib
 import json
@@ -101,10 +104,10 @@ def train_digests():
             out[f"ce_rows {form} {B_} {T_} {A_}"] = sha(dpr, part, acc)
     # 4. the fused steps (the blobs after AdamW, the gradient blobs, the losses)
     for E in (32, 18):
-        def model(seed, H_):
+        def model(seed, H_, dropout=0.0):
             torch.manual_seed(seed)
-            return Transformer(dict(horizon=H_, state_dim=1, action_dim=A, n_layer=L, n_embd=E, n_head=1, dropout=0.0,
-                                    test=False)).cuda().train()
+            return Transformer(dict(horizon=H_, state_dim=1, action_dim=A, n_layer=L, n_embd=E, n_head=1,
+                                    dropout=dropout, test=False)).cuda().train()
 
         rs = np.random.RandomState(E)
         t = tr.Trainer(model(1, 8), lr=1e-3)
@@ -119,7 +122,128 @@ def train_digests():
         recs = t.step(means, 6, 0.3, "bernoulli", 0.5, seed=6)
         out[f"explore E{E}"] = sha(t.explorer_blob, t.exploiter_blob, t.explorer_dblob, t.exploiter_dblob,
                                    t.loss_explorer, t.loss_exploiter, *recs)
+        trainer_digests(out, tr, model, E, A, L)
     return out
+
+
+def image_arrays(rs, n, H, sd, A):
+    """a collated batch dict for DeviceImageData.from_arrays (the images count as normalised already)"""
+    import torch
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
+    return {"query_states": f32(rs.normal(size=(n, sd))), "context_states": f32(rs.normal(size=(n, H, sd))),
+            "context_actions": f32(np.eye(A)[rs.randint(0, A, (n, H))]),
+            "context_rewards": f32(rs.normal(size=(n, H))), "optimal_actions": f32(np.eye(A)[rs.randint(0, A, n)]),
+            "query_images": f32(rs.normal(size=(n, 3, 25, 25))),
+            "context_images": f32(rs.normal(size=(n, H, 3, 25, 25)))}
+
+
+def trainer_digests(out, tr, model, E, A, L):
+    """Group 4 continued: the four trainer classes through their public surface alone -- three steps (the
+    second on a smaller batch), ``eval_loss``, dropout seeds from the CUDA generator and passed in, chunked
+    gradients, and the state after a rejected call.  ``model(seed, H, dropout)``: a Transformer."""
+    import torch
+    from models.net import ImageTransformer
+
+    def weights(*modules):
+        return [q for m in modules for _, q in sorted(m.state_dict().items())]
+
+    def rejected(name, t, blob, call):
+        """a call the trainer must refuse, then (by the caller) a good one: steps and blob stay"""
+        steps, before = t.steps, blob.clone()
+        try:
+            call()
+        except ValueError:
+            pass
+        else:
+            raise AssertionError(f"{name}: the call was not rejected")
+        out[name] = sha(blob, torch.tensor([t.steps, steps, int(torch.equal(blob, before))]))
+
+    # Trainer: batches of 6, 4 (with a perm) and 6 samples, then the test loss; dropout seeds are drawn per call
+    H = 8
+    for p in (0.0, 0.1):
+        rs = np.random.RandomState(100 + E)
+        data = step_data(rs, 12, H, 1, A)
+        perm = np.stack([rs.permutation(H) for _ in range(4)])
+        t = tr.Trainer(model(5, H, p), lr=1e-3)
+        torch.cuda.manual_seed(1)
+        t.step(data, np.arange(0, 6))
+        t.step(data, np.arange(6, 10), perm=perm)
+        t.step(data, np.arange(3, 9))
+        t.eval_loss(data, np.arange(1, 6))
+        out[f"Trainer E{E} drop{p} steps 6,4p,6 + eval"] = sha(t.blob, t.m, t.v, t.loss, torch.tensor([t.steps]))
+        if p == 0.0:
+            rejected(f"Trainer E{E} rejects action_dim", t, t.blob,
+                     lambda: t.step(step_data(rs, 4, H, 1, A + 1), np.arange(4)))
+            rejected(f"Trainer E{E} rejects a window above n_positions", t, t.blob,
+                     lambda: t.step(step_data(rs, 4, 5 * H, 1, A), np.arange(4)))
+            rejected(f"Trainer E{E} rejects perm", t, t.blob, lambda: t.eval_loss(data, np.arange(4), perm=perm[:3]))
+            t.step(data, np.arange(2, 7))
+            out[f"Trainer E{E} step after the rejected ones"] = sha(t.blob, t.m, t.v, t.loss, torch.tensor([t.steps]))
+    # ImageTrainer on 6 synthetic samples of horizon 3
+    sd, Hi = 2, 3
+    for p, seeds, name in ((0.0, None, "drop0.0"), (0.1, (11, 12, 13, 14), "drop0.1 seed="),
+                           (0.1, None, "drop0.1 seed=None")):
+        rs = np.random.RandomState(200 + E)
+        data = tr.DeviceImageData.from_arrays(image_arrays(rs, 6, Hi, sd, A))
+        perm = np.stack([rs.permutation(Hi) for _ in range(2)])
+        torch.manual_seed(6)
+        t = tr.ImageTrainer(ImageTransformer(dict(
+            horizon=Hi, state_dim=sd, action_dim=A, n_layer=L, n_embd=E, n_head=1, shuffle=False, dropout=p, test=False,
+            store_gpu=False, image_size=25)).cuda().train(), lr=1e-3)
+        torch.cuda.manual_seed(1)
+        s = seeds or (None,) * 4
+        t.step(data, np.arange(0, 4), seed=s[0])
+        t.step(data, np.arange(4, 6), perm=perm, seed=s[1])
+        t.step(data, np.arange(1, 5), seed=s[2])
+        t.eval_loss(data, np.arange(0, 3), seed=s[3])
+        state = (t.blob, t.front_blob, t.m, t.v, t.front_m, t.front_v, t.loss)
+        out[f"ImageTrainer E{E} {name} steps 4,2p,4 + eval"] = sha(*state, torch.tensor([t.steps]))
+        if p == 0.0:
+            rejected(f"ImageTrainer E{E} rejects action_dim", t, t.front_blob,
+                     lambda: t.step(tr.DeviceImageData.from_arrays(image_arrays(rs, 2, Hi, sd, A + 1)), np.arange(2)))
+            t.step(data, np.arange(2, 5))
+            out[f"ImageTrainer E{E} step after the rejected one"] = sha(*state, torch.tensor([t.steps]))
+            out[f"ImageTrainer E{E} sync_to_model"] = sha(*weights(t.sync_to_model()))
+    # the bandit pair: 8 envs, then 5 (another workspace), then 8; K = 6 (window 6 of n_positions 36)
+    K = 6
+    rs = np.random.RandomState(300 + E)
+    means = rs.uniform(0, 1, (8, A))
+    u5, g5 = rs.uniform(0, 1, (K - 1, 5)), rs.standard_normal((K - 1, 5))
+    ea8 = rs.randint(0, A, (K - 1, 8)).astype(np.int32)
+    for chunk in (0, 3):
+        for fw in (False, True):
+            t = tr.InteractiveTrainer(model(7, 8), lr=1e-3, chunk=chunk, full_width=fw)
+            recs = list(t.step(means, K, 0.3, "uniform", seed=21))
+            recs += t.step(means[:5], K, 0.3, "bernoulli", uniforms=u5, noise=g5, targets=np.arange(5) % A)
+            recs += t.step(means, K, 0.3, "uniform", seed=22)
+            out[f"InteractiveTrainer E{E} chunk{chunk} full_width{int(fw)} envs 8,5,8"] = sha(
+                t.blob, t.m, t.v, t.dblob, t.loss, torch.tensor([t.steps]), *recs)
+        rejected(f"InteractiveTrainer E{E} chunk{chunk} rejects uniforms", t, t.blob,
+                 lambda: t.step(means, K, 0.3, "uniform", uniforms=u5))
+        rejected(f"InteractiveTrainer E{E} chunk{chunk} rejects K above n_positions", t, t.blob,
+                 lambda: t.step(means, 37, 0.3, "uniform", seed=1))
+        t.step(means, K, 0.3, "uniform", seed=23)
+        out[f"InteractiveTrainer E{E} chunk{chunk} step after the rejected ones"] = sha(
+            t.blob, t.m, t.v, t.dblob, t.loss, torch.tensor([t.steps]))
+        out[f"InteractiveTrainer E{E} chunk{chunk} sync_to_model"] = sha(*weights(t.sync_to_model()))
+        for inject in (False, True):
+            t = tr.ExploreExploitTrainer(model(8, 8), model(9, 8), lr=1e-3, chunk=chunk)
+            recs = list(t.step(means, K, 0.3, "bernoulli", 0.5, seed=31, env_actions=ea8 if inject else None))
+            recs += t.step(means[:5], K, 0.3, "uniform", 0.5, uniforms=u5, noise=g5)
+            recs += t.step(means, K, 0.3, "bernoulli", 2.0, seed=32)
+            blobs = (t.explorer_blob, t.exploiter_blob, t.explorer_dblob, t.exploiter_dblob)
+            out[f"ExploreExploitTrainer E{E} chunk{chunk} env_actions{int(inject)} envs 8,5,8"] = sha(
+                *blobs, t.loss_explorer, t.loss_exploiter, torch.tensor([t.steps]), *recs)
+        rejected(f"ExploreExploitTrainer E{E} chunk{chunk} rejects env_actions", t, t.explorer_blob,
+                 lambda: t.step(means, K, 0.3, "uniform", 1.0, env_actions=ea8[:, :5]))
+        rejected(f"ExploreExploitTrainer E{E} chunk{chunk} rejects beta", t, t.exploiter_blob,
+                 lambda: t.step(means, K, 0.3, "uniform", 0.0, seed=1))
+        t.step(means, K, 0.3, "uniform", 1.0, seed=33)
+        losses = t.read_losses()
+        out[f"ExploreExploitTrainer E{E} chunk{chunk} step after the rejected ones"] = sha(
+            *blobs, torch.tensor(losses, dtype=torch.float64), t.loss_explorer, t.loss_exploiter,
+            torch.tensor([t.steps]))
+        out[f"ExploreExploitTrainer E{E} chunk{chunk} sync_to_models"] = sha(*weights(*t.sync_to_models()))
 
 
 def step_data(rs, n, H, sd, A):
@@ -157,7 +281,40 @@ def train_child(lib):
         b.record()
         torch.cuda.synchronize()
         ms[name] = a.elapsed_time(b) / steps
-    print(json.dumps({"lib": lib, "digests": digests, "ms": ms}))
+    print(json.dumps({"lib": lib, "digests": digests, "ms": ms, "host_us": host_us_per_step(tr)}))
+
+
+def host_us_per_step(tr, steps=200):
+    """{trainer: wall microseconds to enqueue one step}, over ``steps`` steps without a synchronisation, at
+    shapes where the Python layer is the cost: width 32, 2 layers, 5 arms, 8 samples / envs, window 9."""
+    import time
+    import torch
+    from models.net import ImageTransformer, Transformer
+    A, H, n = 5, 8, 8
+    cfg = dict(horizon=H, action_dim=A, n_layer=2, n_embd=32, n_head=1, dropout=0.0, test=False)
+    rs = np.random.RandomState(0)
+    torch.manual_seed(0)
+    bandit = [Transformer(dict(cfg, state_dim=1)).cuda().train() for _ in range(4)]
+    image = ImageTransformer(dict(cfg, state_dim=2, shuffle=False, store_gpu=False, image_size=25)).cuda().train()
+    means, idx = torch.from_numpy(rs.uniform(0, 1, (n, A))).cuda(), torch.arange(n).cuda()
+    t0, t1 = tr.Trainer(bandit[0], lr=1e-4), tr.ImageTrainer(image, lr=1e-4)
+    d0 = t0.device_data(step_data(rs, 12, H, 1, A))
+    d1 = tr.DeviceImageData.from_arrays(image_arrays(rs, n, H, 2, A))
+    t2, t3 = tr.InteractiveTrainer(bandit[1], lr=1e-4), tr.ExploreExploitTrainer(bandit[2], bandit[3], lr=1e-4)
+    out = {}
+    seeds = iter(range(10 ** 6))
+    for name, step in (("Trainer", lambda: t0.step(d0, idx)), ("ImageTrainer", lambda: t1.step(d1, idx)),
+                       ("InteractiveTrainer", lambda: t2.step(means, H + 1, 0.3, "uniform", seed=next(seeds))),
+                       ("ExploreExploitTrainer", lambda: t3.step(means, H + 1, 0.3, "uniform", 1.0, seed=next(seeds)))):
+        for _ in range(20):
+            step()
+        torch.cuda.synchronize()
+        start = time.perf_counter()
+        for _ in range(steps):
+            step()
+        out[name] = (time.perf_counter() - start) / steps * 1e6
+        torch.cuda.synchronize()
+    return out
 
 
 def train_parent(libs):
@@ -171,16 +328,23 @@ def train_parent(libs):
             if cp.returncode:
                 sys.exit(f"{lib}: child failed ({cp.returncode})\n{cp.stderr[-3000:]}")
             d = json.loads(cp.stdout.strip().splitlines()[-1])
-            rounds[lib].append(d["ms"])
+            rounds[lib].append({"ms_per_step": d["ms"], "host_us_per_step": d["host_us"]})
+            print(f"round {rnd} {lib}: {rounds[lib][-1]}", file=sys.stderr, flush=True)
             same = same and dig.setdefault(lib, d["digests"]) == d["digests"]  # the same library, run to run
     ref = dig[libs[0]]
     diff = sorted(k for lib in libs for k in set(ref) | set(dig[lib]) if ref.get(k) != dig[lib].get(k))
     res = {"digest_cases": len(ref), "digests_equal": same and not diff, "differing": diff,
-           "steps_per_round": int(os.environ.get("AB_STEPS", "300")), "ms_per_step": {}}
+           "steps_per_round": int(os.environ.get("AB_STEPS", "300")), "ms_per_step": {}, "host_us_per_step": {}}
     for lib, rs_ in rounds.items():
-        res["ms_per_step"][lib] = {
-            shape: {"rounds": [round(r[shape], 5) for r in rs_], "median": float(np.median([r[shape] for r in rs_])),
-                    "min": min(r[shape] for r in rs_), "max": max(r[shape] for r in rs_)} for shape in rs_[0]}
+        for what in ("ms_per_step", "host_us_per_step"):
+            per = {k: [r[what][k] for r in rs_] for k in rs_[0][what]}
+            res[what][lib] = {k: {"rounds": [round(x, 5) for x in v], "median": float(np.median(v)), "min": min(v),
+                                  "max": max(v)} for k, v in per.items()}
+    # every later argument against the first: its median may exceed the first's by the first's own spread
+    res["over_margin"] = [
+        f"{what} {k} {lib}" for what in ("ms_per_step", "host_us_per_step") for lib in libs[1:]
+        for k, base in res[what][libs[0]].items()
+        if res[what][lib][k]["median"] - base["median"] > base["max"] - base["min"]]
     out = os.environ.get("AB_OUT", os.path.join(ROOT, "profiles", "train_refactor"))
     os.makedirs(out, exist_ok=True)
     with open(os.path.join(out, "digests.txt"), "w") as f:
@@ -191,12 +355,19 @@ def train_parent(libs):
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res))
-    sys.exit(0 if res["digests_equal"] else 1)
+    sys.exit(0 if res["digests_equal"] else 1)  # (over_margin is reported, not enforced: read it)
 
 
 def child(lib):
     sys.path[:0] = [os.path.join(ROOT, "decision-pretrained-transformer_amd"), ROOT]
     from dpt_hip import _lib
+    if "@" in lib:  # "libX.so@<file>.py": that file stands in for dpt_hip/train.py (an A/B of the Python layer)
+        import importlib.util
+        import dpt_hip
+        lib, path = lib.split("@", 1)
+        spec = importlib.util.spec_from_file_location("dpt_hip.train", os.path.join(ROOT, path))
+        dpt_hip.train = sys.modules["dpt_hip.train"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(dpt_hip.train)
     ybits = None  # "libX.so+y32" / "+y24": DPT_TUNE_YCACHE_BITS (the last suffix)
     for suf, bits in (("+y32", 32), ("+y24", 24)):
         if lib.endswith(suf):

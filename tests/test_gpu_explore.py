@@ -517,7 +517,7 @@ def test_explore_trainer_rejects_what_it_cannot_run():
         t.step(np.full((2, 5), 0.5), 3, VAR, "uniform", 0.0)
     with pytest.raises(ValueError, match="env_actions"):
         t.step(np.full((2, 5), 0.5), 3, VAR, "uniform", 1.0, env_actions=np.zeros((3, 2), np.int32))
-    assert t.steps == 0 and not t._state["explorer"][1].any() and not t._state["exploiter"][1].any()
+    assert t.steps == 0 and not t.explorer_state.m.any() and not t.exploiter_state.m.any()
 
 
 # ----------------------------------------------------------------------------- command line
