@@ -442,6 +442,49 @@ def regret_max_steps():
     return n.value
 
 
+# ----------------------------------------------------------------------------- explore-then-exploit evaluation
+
+def recommend_curve(logits, means, targets=None):
+    """dpt_recommend_curve: logits (N, T, A) fp32 (row t = the recommender after t transitions), means
+    (N, A), targets (N) the optimal arms (default: ``means.argmax(1)``) -> dict of device tensors
+    greedy_arm (N, T) int32, greedy_value / expected_value / p_opt (N, T) float64."""
+    dev = device()
+    lg = _dev(logits, torch.float32, dev)
+    means_d = _dev(means, torch.float64, dev)
+    if lg.dim() != 3 or means_d.dim() != 2 or tuple(means_d.shape) != (lg.shape[0], lg.shape[2]):
+        raise ValueError(f"logits {tuple(lg.shape)} / means {tuple(means_d.shape)} are not (N, T, A) / (N, A)")
+    N, T, A = (int(x) for x in lg.shape)
+    tg = means_d.argmax(dim=1) if targets is None else _dev(targets, torch.int64, dev).reshape(-1)
+    if tg.numel() != N:
+        raise ValueError(f"targets {tg.numel()} != tasks {N}")
+    out = dict(greedy_arm=torch.empty((N, T), dtype=torch.int32, device=dev),
+               **{k: torch.empty((N, T), dtype=torch.float64, device=dev)
+                  for k in ("greedy_value", "expected_value", "p_opt")})
+    _lib.call("dpt_recommend_curve", _p(lg), _p(means_d), _p(tg), N, T, A, _p(out["greedy_arm"]),
+              _p(out["greedy_value"]), _p(out["expected_value"]), _p(out["p_opt"]), _stream())
+    out["_keep"] = (lg, means_d, tg)
+    return out
+
+
+def empirical_recommend(actions, rewards, means):
+    """dpt_empirical_recommend: EmpMeanPolicy(online=False) on every prefix of the records actions (N, H)
+    int32 / rewards (N, H) -> dict of device tensors emp_arm (N, H + 1) int32, emp_value (N, H + 1) float64."""
+    dev = device()
+    means_d = _dev(means, torch.float64, dev)
+    acts = _dev(actions, torch.int32, dev)
+    rews = _dev(rewards, torch.float64, dev)
+    if means_d.dim() != 2 or acts.dim() != 2 or acts.shape != rews.shape or acts.shape[0] != means_d.shape[0]:
+        raise ValueError(f"actions {tuple(acts.shape)} / rewards {tuple(rews.shape)} / means {tuple(means_d.shape)} "
+                         f"are not (N, H) / (N, H) / (N, A)")
+    (N, H), A = (int(x) for x in acts.shape), int(means_d.shape[1])
+    out = dict(emp_arm=torch.empty((N, H + 1), dtype=torch.int32, device=dev),
+               emp_value=torch.empty((N, H + 1), dtype=torch.float64, device=dev))
+    _lib.call("dpt_empirical_recommend", _p(acts) if H else None, _p(rews) if H else None, _p(means_d), N, H, A,
+              _p(out["emp_arm"]), _p(out["emp_value"]), _stream())
+    out["_keep"] = (acts, rews, means_d)
+    return out
+
+
 def set_decode_tile(tile):
     """Tasks per workgroup of the decode kernels (8: two workgroups per CU; 16: one)."""
     _lib.call("dpt_tuning_set", _lib.TUNE_DECODE_TILE, int(tile))

@@ -277,6 +277,22 @@ SIGNATURES["dpt_explore_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i32, c
 SIGNATURES["dpt_explore_grad"] = (_i32, [_train_desc_p, _c_void_p, _c_void_p, ctypes.POINTER(ExploreArgs), _c_void_p])
 
 
+class ExploitEvalArgs(ctypes.Structure):
+    """dpt_exploit_eval_args: one chunk of the explore-then-exploit evaluation."""
+    _fields_ = [("N", _i32), ("H", _i32), ("flags", _i32), ("reserved", _i32), ("actions", _c_void_p),
+                ("rewards", _c_void_p), ("means", _c_void_p), ("targets", _c_void_p), ("workspace", _c_void_p),
+                ("logits_out", _c_void_p), ("greedy_arm", _c_void_p), ("greedy_value", _c_void_p),
+                ("expected_value", _c_void_p), ("p_opt", _c_void_p)]
+
+
+SIGNATURES["dpt_recommend_curve"] = (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p,
+                                            _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_empirical_recommend"] = (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p,
+                                                _c_void_p, _c_void_p])
+SIGNATURES["dpt_exploit_eval_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i32, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_exploit_eval"] = (_i32, [_train_desc_p, _c_void_p, ctypes.POINTER(ExploitEvalArgs), _c_void_p])
+
+
 SITE_IMAGE_ENC = 1 << 20  # Philox site of the image encoder's dropout (DPT_SITE_IMAGE_ENC)
 
 

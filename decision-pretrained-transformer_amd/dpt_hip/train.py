@@ -24,6 +24,9 @@ master blob, the window packed from its records, forward, last-position cross-en
 ``ExploreExploitTrainer`` (train_explorer_exploiter.py; dpt_explore_grad: the explorer's rollout with the
 env stepped apart, one pack, both models' forward / every-position cross-entropy / backward with the
 advantage weights in between).
+
+``exploit_curve`` is the evaluation of that last stage (dpt_exploit_eval): the exploiter's recommendation
+after every budget of someone's recorded pulls, from one forward over the final window.
 """
 import ctypes
 
@@ -771,6 +774,64 @@ def chunk_plan(n, chunk):
     return [(off, min(size, n - off)) for off in range(0, n, size)]
 
 
+def exploit_curve(model, actions, rewards, means, targets=None, chunk=0, blob=None, want_logits=False):
+    """The explore-then-exploit curve of ``model`` (the exploiter) on someone's records: what it
+    recommends after every budget t = 0 .. H of the pulls actions (N, H) int32 / rewards (N, H), for the
+    bandits means (N, A) with optimal arms ``targets`` (default: ``means.argmax(1)``).  One
+    dpt_exploit_eval per chunk of tasks (``chunk_plan(N, chunk)``: the pack, ONE forward-only forward at
+    every position of the (1 + H)-token window -- row t is the model after t transitions -- and
+    dpt_recommend_curve), on one workspace sized for the first chunk, with no host synchronisation.
+    ``blob``: run on this packed blob (a trainer's master weights) instead of the module's parameters.
+    Returns a dict of device tensors: greedy_arm (N, H + 1) int32, greedy_value / expected_value / p_opt
+    (N, H + 1) float64 and, with ``want_logits``, logits (N, H + 1, A) float32."""
+    if model.state_dim != 1:
+        raise ValueError(f"exploit_curve: state_dim={model.state_dim} (bandits have state_dim 1)")
+    if model.dropout > 0 and model.training:
+        raise ValueError("exploit_curve: the model is in training mode with dropout > 0 (call model.eval(): the "
+                         "evaluation forward has no dropout masks)")
+    if int(chunk) < 0:
+        raise ValueError(f"exploit_curve: chunk={chunk}")
+    dev, A = device(), model.action_dim
+    means_d = _dev(means, torch.float64, dev)
+    if means_d.dim() != 2 or means_d.shape[1] != A or means_d.shape[0] < 1:
+        raise ValueError(f"means {tuple(means_d.shape)} != (N >= 1, action_dim {A})")
+    N = int(means_d.shape[0])
+    acts, rews = _dev(actions, torch.int32, dev), _dev(rewards, torch.float64, dev)
+    if acts.dim() != 2 or acts.shape[0] != N or acts.shape != rews.shape:
+        raise ValueError(f"actions {tuple(acts.shape)} / rewards {tuple(rews.shape)} != (N = {N}, H) each")
+    H = int(acts.shape[1])
+    tg = means_d.argmax(dim=1) if targets is None else _dev(targets, torch.int64, dev).reshape(-1)
+    if tg.numel() != N:
+        raise ValueError(f"targets {tg.numel()} != tasks {N}")
+    if blob is None:
+        blob = pack_params(param_list(model), dev)
+    _on_device(blob)
+    d = desc(model.n_layer, model.n_embd, model.state_dim, A, model.n_positions, 1, 1)
+    plan = chunk_plan(N, chunk)
+    need = ctypes.c_int64()
+    _lib.call("dpt_exploit_eval_workspace_numel", ctypes.byref(d), plan[0][1], H, ctypes.byref(need))
+    try:
+        ws = torch.empty(need.value, dtype=torch.float32, device=dev)
+    except torch.cuda.OutOfMemoryError as e:
+        raise MemoryError(f"exploit_curve: one chunk of {plan[0][1]} envs at K={H + 1} needs a workspace of "
+                          f"{4 * need.value} bytes; pass a smaller `chunk` (now {int(chunk)}; 0 = all envs at "
+                          f"once)") from e
+    out = dict(greedy_arm=torch.empty((N, H + 1), dtype=torch.int32, device=dev),
+               **{k: torch.empty((N, H + 1), dtype=torch.float64, device=dev)
+                  for k in ("greedy_value", "expected_value", "p_opt")})
+    out["logits"] = torch.empty((N, H + 1, A), dtype=torch.float32, device=dev) if want_logits else None
+    for off, n in plan:
+        rows = slice(off, off + n)  # rows of every (N, ...) array: one contiguous block
+        args = _lib.ExploitEvalArgs(
+            n, H, 0, 0, _ptr(acts[rows]) if H else None, _ptr(rews[rows]) if H else None, _ptr(means_d[rows]),
+            _ptr(tg[rows]), _ptr(ws), None if out["logits"] is None else _ptr(out["logits"][rows]),
+            _ptr(out["greedy_arm"][rows]), _ptr(out["greedy_value"][rows]), _ptr(out["expected_value"][rows]),
+            _ptr(out["p_opt"][rows]))
+        _lib.call("dpt_exploit_eval", ctypes.byref(d), _p(blob), ctypes.byref(args), _stream())
+    out["_keep"] = (ws, blob, means_d, acts, rews, tg)
+    return out
+
+
 class _BanditTrainer(_TrainerCore):
     """The fused on-policy bandit episode for models.net.Transformers with state_dim 1 and no dropout: one
     ModelState with a gradient blob per model (``_states``, in the order AdamW updates them).  ``step``
@@ -951,6 +1012,13 @@ class ExploreExploitTrainer(_BanditTrainer):
     def read_losses(self):
         """The accumulated (explorer, exploiter) loss sums (one device synchronisation), then reset."""
         return tuple(self._read_losses())
+
+    def exploit_curve(self, actions, rewards, means, targets=None, chunk=None, want_logits=False):
+        """``exploit_curve`` of the exploiter's master blob as it stands (no ``sync_to_models`` needed) on the
+        records actions / rewards (N, H) of the bandits ``means``; ``chunk`` defaults to the trainer's."""
+        return exploit_curve(self.exploiter, actions, rewards, means, targets=targets,
+                             chunk=self.chunk if chunk is None else chunk, blob=self.exploiter_blob,
+                             want_logits=want_logits)
 
     def sync_to_models(self):
         """Unpack the two master blobs into the modules' parameters (wte is untouched)."""

@@ -48,7 +48,9 @@ extern "C" {
  * DPT (dpt_image_front_*, dpt_train_*_embeds) and its training step (dpt_image_normalize,
  * dpt_image_pack_batch, dpt_image_train_step_workspace_numel, dpt_image_train_step,
  * dpt_image_train_eval_loss); its act step (dpt_image_obs_tables, dpt_image_obs_preprocess,
- * dpt_image_act_workspace_numel, dpt_image_act_set_context, dpt_image_act_step) */
+ * dpt_image_act_workspace_numel, dpt_image_act_set_context, dpt_image_act_step); the explore-then-exploit
+ * evaluation (dpt_recommend_curve, dpt_empirical_recommend, dpt_exploit_eval_workspace_numel,
+ * dpt_exploit_eval) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -691,6 +693,69 @@ int dpt_explore_workspace_numel(const dpt_train_desc* desc_host, int32_t N, int3
  * null or equal gradient blobs. */
 int dpt_explore_grad(const dpt_train_desc* desc_host, const float* explorer_blob, const float* exploiter_blob,
                      const dpt_explore_args* args_host, void* stream);
+
+/* ------------------------------------------------------------------ explore-then-exploit evaluation
+ * What the explorer/exploiter step trains for, measured: after a budget of t = 0 .. H exploratory pulls
+ * the exploiter recommends an arm from those t transitions, and the report is the simple regret
+ * mu* - mu[recommended] as a curve over t.  As in the training step, the exploiter's logits after t
+ * transitions are row t of ONE forward over the final (1 + H)-token window (constant query token at
+ * position 0, causal attention): the whole curve of N tasks is one pack, one forward-only training
+ * forward at every position and one reduction, where the reference's surface (Transformer.forward in
+ * test mode, the last position of a growing window) needs H + 1 forwards.  ABI 8, additive.
+ *
+ * dpt_recommend_curve, per row (i, t) of logits (N, T, A) fp32, means (N, A) fp64, targets (N) int64
+ * (the optimal arm), all arithmetic in fp64 from the fp32 logits with one rounding on the store:
+ *   greedy_arm     (N, T) int32  first index of the maximum logit (np.argmax: the first NaN when there
+ *                                is one); always in [0, A)
+ *   greedy_value   (N, T) fp64   means[i][greedy_arm]
+ *   expected_value (N, T) fp64   sum_a p_a means[i][a], p = softmax(logits[i][t]) with the maximum
+ *                                subtracted: the value of SAMPLING the recommendation
+ *   p_opt          (N, T) fp64   p[targets[i]], 0 for a target outside [0, A)
+ * Any output may be NULL (targets may be NULL when p_opt is).  The value arrays are laid out like
+ * arm_value_out of the rollouts, so dpt_regret_moments(value, opt, N, T, ...) gives the moments of the
+ * simple regret opt - value over tasks.  One launch; A <= 32 (else DPT_EUNSUPPORTED); fixed reduction
+ * order (deterministic).                                                                            */
+int dpt_recommend_curve(const float* logits, const double* means, const int64_t* targets, int32_t N, int32_t T,
+                        int32_t A, int32_t* greedy_arm, double* greedy_value, double* expected_value, double* p_opt,
+                        void* stream);
+/* ctrls/ctrl_bandit.py:91-117, EmpMeanPolicy(online=False), on every prefix of the records actions (N, H)
+ * int32 / rewards (N, H) fp64.  For t = 0 .. H: sum[a] and cnt[a] accumulate over the pulls j < t IN
+ * PULL ORDER in fp64, b_mean = sum / max(1, cnt), emp_arm (N, H + 1) int32 = the first index of its
+ * maximum (arm 0 at t = 0), emp_value (N, H + 1) fp64 = means[i][emp_arm].  An action outside [0, A)
+ * adds to no arm (dpt_interactive_pack packs zeros for it).  H = 0 (actions / rewards may be NULL) is
+ * legal; either output may be NULL.  A <= 32.                                                        */
+int dpt_empirical_recommend(const int32_t* actions, const double* rewards, const double* means, int32_t N,
+                            int32_t H, int32_t A, int32_t* emp_arm, double* emp_value, void* stream);
+
+typedef struct dpt_exploit_eval_args {
+    int32_t N;                 /* tasks of this chunk                                              */
+    int32_t H;                 /* recorded pulls per task (>= 0): budgets 0 .. H                   */
+    int32_t flags;             /* 0                                                                */
+    int32_t reserved;          /* 0                                                                */
+    const int32_t* actions;    /* (N, H) the context actions of the records (NULL when H = 0)      */
+    const double* rewards;     /* (N, H)                                                           */
+    const double* means;       /* (N, A)                                                           */
+    const int64_t* targets;    /* (N) optimal arm (may be NULL when p_opt is)                      */
+    float* workspace;          /* dpt_exploit_eval_workspace_numel floats, 16-byte aligned         */
+    float* logits_out;         /* (N, H + 1, A) the exploiter's logits after every budget, or NULL */
+    int32_t* greedy_arm;       /* (N, H + 1) each, or NULL: as dpt_recommend_curve                 */
+    double* greedy_value;
+    double* expected_value;
+    double* p_opt;
+} dpt_exploit_eval_args;
+
+/* floats of workspace for a chunk of N tasks with H pulls: the forward-only training workspace at
+ * window H + 1, the tokens and the logits */
+int dpt_exploit_eval_workspace_numel(const dpt_train_desc* desc_host, int32_t N, int32_t H, int64_t* numel_out_host);
+/* One chunk of tasks, chained on one stream with no host synchronisation and no allocation, straight
+ * from a packed blob (a module's or a trainer's master blob): dpt_interactive_pack -> dpt_train_forward
+ * (DPT_TRAIN_FORWARD_ONLY, every position, window H + 1) -> dpt_recommend_curve.  desc: the model's
+ * n_layer, n_embd, state_dim, action_dim, n_positions (batch / window / flags are ignored: N and H
+ * rule).  Host checks fail before any launch: null pointers, N < 1, H < 0, 1 + H > n_positions,
+ * state_dim != 1, action_dim > 32 (DPT_EUNSUPPORTED), dropout != 0, non-zero flags / reserved, a
+ * workspace that is not 16-byte aligned. */
+int dpt_exploit_eval(const dpt_train_desc* desc_host, const float* blob, const dpt_exploit_eval_args* args_host,
+                     void* stream);
 
 /* ------------------------------------------------------------------ image-conditioned DPT (ImageTransformer)
  * models/net.py:63-132: per token an image (3, 25, 25) goes through Conv2d(3,16,k3,s2) -> ReLU ->
