@@ -5,6 +5,7 @@
 // ABI (generic controllers / envs driven from Python); the bandit hot loop runs
 // fused inside rollout_bandit_kernel (dpt_decode.hip).
 #include "dpt_common.h"
+#include "dpt_darkroom_env.h"  // darkroom_move, darkroom_opt
 
 namespace dpt {
 
@@ -138,23 +139,6 @@ __device__ inline int philox_randint(uint64_t seed, uint64_t step, int64_t task,
     U4 r = philox(seed, step, task, stream);
     const uint32_t w = word == 0 ? r.x : word == 1 ? r.y : word == 2 ? r.z : r.w;
     return (int)(((uint64_t)w * (uint64_t)n) >> 32);  // multiply-shift, bias < n / 2^32
-}
-
-__device__ inline void darkroom_move(int& x, int& y, int a, int dim) {
-    x += (a == 0) - (a == 1);
-    y += (a == 2) - (a == 3);
-    x = min(max(x, 0), dim - 1);
-    y = min(max(y, 0), dim - 1);
-}
-
-__device__ inline int darkroom_opt(int x, int y, int gx, int gy, const int32_t* perm) {
-    int a = x < gx ? 0 : x > gx ? 1 : y < gy ? 2 : y > gy ? 3 : 4;
-    if (perm) {
-        int k = 0;
-        while (k < 5 && perm[k] != a) ++k;
-        a = k;
-    }
-    return a;
 }
 
 // collect_data.py:83-111 rollin_mdp + generate_mdp_histories_from_envs (:189-218).

@@ -254,6 +254,29 @@ SIGNATURES["dpt_interactive_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i3
 SIGNATURES["dpt_interactive_grad"] = (_i32, [_train_desc_p, _c_void_p, ctypes.POINTER(InteractiveArgs), _c_void_p])
 
 
+MDP_LOSS_NONE = 0  # dpt_interactive_mdp_args.loss_mode: the rollout alone (evaluation)
+MDP_LOSS_LAST = 1  # mean CE of the last step's logits against its expert action (train_interactive.py:134-135)
+MDP_LOSS_EVERY = 2  # mean CE over every step's logits against the expert action at the visited state
+
+
+class InteractiveMDPArgs(ctypes.Structure):
+    """dpt_interactive_mdp_args: one chunk of an interactive (on-policy) DarkRoom training step."""
+    _fields_ = [("N", _i32), ("K", _i32), ("dim", _i32), ("loss_mode", _i32), ("flags", _i32), ("sample", _i32),
+                ("first_task", _i64), ("scale", _f64), ("seed", _u64), ("counter", _u64), ("goal", _c_void_p),
+                ("perm", _c_void_p), ("uniforms", _c_void_p), ("states_out", _c_void_p), ("actions_out", _c_void_p),
+                ("rewards_out", _c_void_p), ("targets_out", _c_void_p), ("workspace", _c_void_p),
+                ("dblob", _c_void_p), ("loss_acc", _c_void_p)]
+
+
+SIGNATURES["dpt_mdp_pack"] = (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p])
+SIGNATURES["dpt_darkroom_act_step"] = (_i32, [_c_void_p, _i32, _i32, _i32, _i32, _i32, _i32, _c_void_p, _u64, _u64,
+                                              _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                              _c_void_p, _c_void_p])
+SIGNATURES["dpt_interactive_mdp_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i32, _i32, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_interactive_mdp_grad"] = (_i32, [_train_desc_p, _c_void_p, ctypes.POINTER(InteractiveMDPArgs),
+                                                 _c_void_p])
+
+
 EXPLORE_ACCUMULATE = 1  # dpt_explore_args.flags: both dblobs += the chunk's gradients
 
 

@@ -12,7 +12,7 @@ holding the forward's saved activations is a torch tensor kept on the autograd c
 image front end (dpt_image_front_forward / _backward: conv encoder, embed_transition, embed_ln) chained
 into the trunk through dpt_train_forward_embeds / dpt_train_backward_embeds.
 
-The four fused trainers keep everything on the device.  ``ModelState`` is one model's master blob with
+The five fused trainers keep everything on the device.  ``ModelState`` is one model's master blob with
 AdamW's ``m`` / ``v`` (and a gradient blob); ``_TrainerCore`` holds the hyper-parameters, the step count
 and the loss accumulator(s).  Under it, ``_DatasetTrainer`` is the one-call step on a device-resident
 dataset: ``Trainer`` (train.py; dpt_train_step on a ``DeviceData``: batch packing, forward, summed
@@ -23,7 +23,10 @@ bandit episode, a gradient call per chunk of envs and then dpt_adamw_step per mo
 master blob, the window packed from its records, forward, last-position cross-entropy, backward) and
 ``ExploreExploitTrainer`` (train_explorer_exploiter.py; dpt_explore_grad: the explorer's rollout with the
 env stepped apart, one pack, both models' forward / every-position cross-entropy / backward with the
-advantage weights in between).
+advantage weights in between).  ``InteractiveMDPTrainer`` is the on-policy DarkRoom episode
+(train_interactive_darkroom.py; dpt_interactive_mdp_grad per chunk of envs: per step the window packed from
+the records, the forward from the master blob, where the loss reads the step the cross-entropy against the
+expert action and the backward, and the act step), and ``rollout_darkroom_interactive`` its loss-free rollout.
 
 ``exploit_curve`` is the evaluation of that last stage (dpt_exploit_eval): the exploiter's recommendation
 after every budget of someone's recorded pulls, from one forward over the final window.
@@ -951,6 +954,150 @@ class InteractiveTrainer(_BanditTrainer):
     def sync_to_model(self):
         """Unpack the master blob into the module's parameters."""
         return _sync(self.state, self.model)
+
+
+MDP_LOSS = {"none": _lib.MDP_LOSS_NONE, "last": _lib.MDP_LOSS_LAST, "every": _lib.MDP_LOSS_EVERY}
+
+
+def _mdp_check_model(model, who):
+    if (model.state_dim, model.action_dim) != (2, 5):
+        raise ValueError(f"{who}: state_dim={model.state_dim} action_dim={model.action_dim} (DarkRoom has state_dim 2, "
+                         f"action_dim 5)")
+    return desc(model.n_layer, model.n_embd, model.state_dim, model.action_dim, model.n_positions, 1, 1)
+
+
+def _mdp_workspace(d, n, K, mode, dev, who, chunk):
+    """The workspace of one chunk of ``n`` envs over ``K`` steps (dpt_interactive_mdp_workspace_numel floats)."""
+    need = ctypes.c_int64()
+    _lib.call("dpt_interactive_mdp_workspace_numel", ctypes.byref(d), n, K, mode, ctypes.byref(need))
+    try:
+        return torch.empty(need.value, dtype=torch.float32, device=dev)
+    except torch.cuda.OutOfMemoryError as e:
+        raise MemoryError(f"{who}: one chunk of {n} envs at K={K} needs a workspace of {4 * need.value} bytes; pass "
+                          f"a smaller `chunk` (now {chunk}; 0 = all envs at once)") from e
+
+
+def _mdp_episode(goals, K, perm, uniforms, seed, dev):
+    """The episode's inputs on the device, validated: (goals (N, 2) int32, perm (N, 5) int32 or None,
+    uniforms (K - 1, N) float64 or None, the 64-bit seed)."""
+    from . import next_seed
+    if K < 1:
+        raise ValueError(f"K={K} (at least 1)")
+    g = _dev(goals, torch.int32, dev)
+    if g.dim() != 2 or g.shape[1] != 2 or g.shape[0] < 1:
+        raise ValueError(f"goals {tuple(g.shape)} != (N >= 1, 2)")
+    N = int(g.shape[0])
+    pm = None if perm is None else _dev(perm, torch.int32, dev)
+    if pm is not None and tuple(pm.shape) != (N, 5):
+        raise ValueError(f"perm {tuple(pm.shape)} != (N = {N}, 5)")
+    u = None if uniforms is None else _dev(uniforms, torch.float64, dev)
+    if u is not None and tuple(u.shape) != (K - 1, N):
+        raise ValueError(f"uniforms {tuple(u.shape)} != (K - 1 = {K - 1}, N = {N})")
+    return g, pm, u, (next_seed() if seed is None else int(seed)) & (2 ** 64 - 1)
+
+
+def _mdp_run(d, blob, ws_for, chunk, mode, goals, K, dim, sample, perm, uniforms, seed, dblob=None, loss=None):
+    """dpt_interactive_mdp_grad once per chunk of envs (``chunk_plan``; first_task = the chunk's offset, so
+    the Philox records do not depend on the chunking; chunk 0 writes ``dblob``, later chunks add to it) on the
+    workspace ``ws_for(chunk 0's envs)``.  Returns the records: states (N, K, 2), actions (N, K - 1), rewards
+    (N, K - 1), targets (N, K), int32 device tensors."""
+    N, dev = int(goals.shape[0]), goals.device
+    rec = dict(states=torch.empty((N, K, 2), dtype=torch.int32, device=dev),
+               actions=torch.empty((N, K - 1), dtype=torch.int32, device=dev),
+               rewards=torch.empty((N, K - 1), dtype=torch.int32, device=dev),
+               targets=torch.empty((N, K), dtype=torch.int32, device=dev))
+    plan = chunk_plan(N, chunk)
+    ws = ws_for(plan[0][1])
+    scale = 1.0 / (N * K) if mode == _lib.MDP_LOSS_EVERY else 1.0 / N
+    for i, (off, n) in enumerate(plan):
+        rows = slice(off, off + n)  # rows of every (N, ...) array: one contiguous block; the uniforms' columns are copied
+        u_c = None if uniforms is None else uniforms[:, rows].contiguous()
+        args = _lib.InteractiveMDPArgs(
+            n, K, int(dim), mode, _lib.INTERACTIVE_ACCUMULATE if i > 0 else 0, int(bool(sample)), off, scale, seed, 0,
+            _ptr(goals[rows]), None if perm is None else _ptr(perm[rows]), _ptr(u_c), _ptr(rec["states"][rows]),
+            _ptr(rec["actions"][rows]) if K > 1 else None, _ptr(rec["rewards"][rows]) if K > 1 else None,
+            _ptr(rec["targets"][rows]), _ptr(ws), _ptr(dblob), _ptr(loss))
+        _lib.call("dpt_interactive_mdp_grad", ctypes.byref(d), _p(blob), ctypes.byref(args), _stream())
+    return rec
+
+
+class InteractiveMDPTrainer(_TrainerCore):
+    """The fused interactive (on-policy) DarkRoom step for a models.net.Transformer with state_dim 2,
+    action_dim 5 and no dropout: one dpt_interactive_mdp_grad per chunk of envs -- for each of the K steps
+    the window packed from the records so far, the forward from the master blob, on a loss-bearing step the
+    cross-entropy against the expert action at the visited state and the backward, and the act step -- then
+    one dpt_adamw_step.  ``loss``: 'every' (the mean over all N K visited states) or 'last' (the mean over
+    the N last states: train_interactive.py:134-135 transliterated)."""
+    blob, m, v, dblob = _of("state", "blob"), _of("state", "m"), _of("state", "v"), _of("state", "dblob")
+
+    def __init__(self, model, lr, weight_decay=1e-4, chunk=0, loss="every", betas=(0.9, 0.999), eps=1e-8):
+        name = type(self).__name__
+        d = _mdp_check_model(model, name)
+        if model.dropout != 0:
+            raise ValueError(f"{name}: dropout must be 0 (the fused path draws no dropout masks)")
+        if int(chunk) < 0:
+            raise ValueError(f"{name}: chunk={chunk}")
+        if loss not in ("every", "last"):
+            raise ValueError(f"{name}: loss={loss!r} ('every' or 'last')")
+        super().__init__(lr, weight_decay, betas, eps)
+        self.model, self.chunk, self.loss_mode, self._d = model, int(chunk), MDP_LOSS[loss], d
+        self.state = ModelState(pack_params(param_list(model), self.loss.device), grad=True)
+        self._ws_shape = (0, 0)  # (chunk envs, K) the workspace was sized for
+
+    def _workspace(self, n, K):
+        if self._ws is None or self._ws_shape != (n, K):
+            self._ws = None  # release the old one first
+            self._ws = _mdp_workspace(self._d, n, K, self.loss_mode, self.loss.device, type(self).__name__, self.chunk)
+            self._ws_shape = (n, K)
+        return self._ws
+
+    def step(self, goals, K, dim, sample=True, perm=None, uniforms=None, seed=None):
+        """One episode of K steps from s_0 = (0, 0): ``goals`` (N, 2) int32 in [0, dim), ``perm`` (N, 5) the
+        action permutations dpt_darkroom_step takes, ``sample`` False for greedy actions.  ``uniforms``
+        (K - 1, N) inject the selection uniforms; otherwise Philox keyed by ``seed`` (default:
+        dpt_hip.next_seed()) and the env's global index.  Adds the step's mean loss to the accumulator and
+        returns the records: a dict of int32 device tensors states (N, K, 2), actions (N, K - 1), rewards
+        (N, K - 1) and targets (N, K)."""
+        K = int(K)
+        g, pm, u, seed = _mdp_episode(goals, K, perm, uniforms, seed, self.loss.device)
+        rec = _mdp_run(self._d, self.state.blob, lambda n: self._workspace(n, K), self.chunk, self.loss_mode, g, K, dim,
+                       sample, pm, u, seed, self.state.dblob, self.loss)
+        self.steps += 1
+        self.state.adamw(self._adamw_args())
+        return rec
+
+    def rollout(self, goals, K, dim, sample=False, perm=None, uniforms=None, seed=None):
+        """``rollout_darkroom_interactive`` of the master blob as it stands (no ``sync_to_model`` needed)."""
+        return rollout_darkroom_interactive(self.model, goals, K, dim, sample, perm=perm, uniforms=uniforms, seed=seed,
+                                            chunk=self.chunk, blob=self.state.blob)
+
+    def sync_to_model(self):
+        """Unpack the master blob into the module's parameters."""
+        return _sync(self.state, self.model)
+
+
+def rollout_darkroom_interactive(model, goals, K, dim, sample=True, perm=None, uniforms=None, seed=None, chunk=0,
+                                 blob=None):
+    """The in-episode DarkRoom rollout of ``InteractiveMDPTrainer.step`` without a loss
+    (dpt_interactive_mdp_grad, DPT_MDP_LOSS_NONE: K forward-only forwards and K - 1 act steps per chunk of
+    envs, no host synchronisation).  ``blob``: run on this packed blob (a trainer's master weights) instead
+    of the module's parameters.  Returns (the records dict of ``step``, the per-env return (N) int64 = the
+    sum of the K - 1 rewards)."""
+    who = "rollout_darkroom_interactive"
+    d = _mdp_check_model(model, who)
+    if model.dropout > 0 and model.training:
+        raise ValueError(f"{who}: the model is in training mode with dropout > 0 (call model.eval(): the rollout's "
+                         f"forwards have no dropout masks)")
+    if int(chunk) < 0:
+        raise ValueError(f"{who}: chunk={chunk}")
+    dev, K = device(), int(K)
+    g, pm, u, seed = _mdp_episode(goals, K, perm, uniforms, seed, dev)
+    if blob is None:
+        blob = pack_params(param_list(model), dev)
+    _on_device(blob)
+    rec = _mdp_run(d, blob, lambda n: _mdp_workspace(d, n, K, _lib.MDP_LOSS_NONE, dev, who, int(chunk)), int(chunk),
+                   _lib.MDP_LOSS_NONE, g, K, dim, sample, pm, u, seed)
+    return rec, rec["rewards"].sum(dim=1)
 
 
 class ExploreExploitTrainer(_BanditTrainer):

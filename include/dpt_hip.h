@@ -50,7 +50,8 @@ extern "C" {
  * dpt_image_train_eval_loss); its act step (dpt_image_obs_tables, dpt_image_obs_preprocess,
  * dpt_image_act_workspace_numel, dpt_image_act_set_context, dpt_image_act_step); the explore-then-exploit
  * evaluation (dpt_recommend_curve, dpt_empirical_recommend, dpt_exploit_eval_workspace_numel,
- * dpt_exploit_eval) */
+ * dpt_exploit_eval); the interactive DarkRoom training step (dpt_mdp_pack, dpt_darkroom_act_step,
+ * dpt_interactive_mdp_workspace_numel, dpt_interactive_mdp_grad) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -607,6 +608,87 @@ int dpt_interactive_workspace_numel(const dpt_train_desc* desc_host, int32_t N, 
  * action_dim > 32 (DPT_EUNSUPPORTED), dropout != 0, a workspace that is not 16-byte aligned. */
 int dpt_interactive_grad(const dpt_train_desc* desc_host, const float* blob, const dpt_interactive_args* args_host,
                          void* stream);
+
+/* ------------------------------------------------------------------ interactive DarkRoom (MDP) training step
+ * The on-policy episode of train_interactive.py:92-143 for the DarkRoom MDP (the reference runs it for
+ * bandits only, :54-55).  N envs with goals (N, 2) in [0, dim), state_dim 2, action_dim 5, s_0 = (0, 0).
+ * For t = 0 .. K - 1:
+ *   W_t (N, t + 1, 10) fp32: row 0 = [s_t | 0_5 | 0_2 | 0], row 1 + j = [s_j | onehot(a_j) | s_{j+1} | r_j]
+ *     for j < t in time order (models/net.py:42-54 on the transitions so far; small integers: exact);
+ *   logits_t (N, 5) = the model's last position on W_t; target_t = opt_action(s_t)
+ *     (envs/darkroom_env.py:69-82, permuted :105-111);
+ *   for t < K - 1: a_t = dpt_select_action's rule on logits_t (sampled at temp 1 with uniforms[t][i] or
+ *     Philox(seed, (counter + t, first_task + i, DPT_STREAM_SELECT)); greedy: first argmax), then
+ *     (s_{t+1}, r_t) = dpt_darkroom_step(s_t, a_t).  The K-th action is never drawn.
+ * The actions are data: no gradient flows through the selection.  In an MDP the query state changes every
+ * step and sits at position 0, so no cached decode exists: every step is a forward over its whole window.
+ * ABI 8, additive.                                                                               */
+
+/* tokens (N, t + 1, 10) = W_t from the records states (N, K, 2), actions (N, K - 1), rewards (N, K - 1)
+ * int32, 0 <= t < K (t = 0 reads no action or reward: both may be NULL when K = 1).  One thread per
+ * output float, copies and int -> float conversions only: bit-exact.  An action outside [0, 5) packs a
+ * zero one-hot. */
+int dpt_mdp_pack(const int32_t* states, const int32_t* actions, const int32_t* rewards, int32_t N, int32_t K,
+                 int32_t t, float* tokens, void* stream);
+/* Step t < K - 1 of the episode for N envs in one launch, one thread per env: reads the env's
+ * last-position row of logits (N, window, 5) (row stride window * 5), selects a_t (sample 1: the step's
+ * uniforms (N) or NULL -> Philox(seed, (counter, first_task + i, DPT_STREAM_SELECT)); sample 0: first
+ * argmax), moves from states[i][t], and writes actions[i][t], rewards[i][t], states[i][t + 1] and
+ * targets[i][t + 1] = opt_action(s_{t+1}) (also into target_next (N) int64 when given:
+ * dpt_train_ce_last's class indices of the next step).  Bit-equal to dpt_select_action (temp 1) ->
+ * dpt_darkroom_step -> dpt_darkroom_opt_action. */
+int dpt_darkroom_act_step(const float* logits, int32_t N, int32_t window, int32_t K, int32_t t, int32_t dim,
+                          int32_t sample, const double* uniforms, uint64_t seed, uint64_t counter,
+                          int64_t first_task, const int32_t* goal, const int32_t* perm, int32_t* states,
+                          int32_t* actions, int32_t* rewards, int32_t* targets, int64_t* target_next,
+                          void* stream);
+
+/* dpt_interactive_mdp_args.loss_mode; N below = the envs of the whole step, not of a chunk */
+#define DPT_MDP_LOSS_NONE 0  /* the rollout alone (evaluation): dblob and loss_acc may be NULL            */
+#define DPT_MDP_LOSS_LAST 1  /* (1 / N) sum_i CE(logits_{K-1,i}, target_{K-1,i}): train_interactive.py:134-135 */
+#define DPT_MDP_LOSS_EVERY 2 /* (1 / (N K)) sum_t sum_i CE(logits_{t,i}, target_{t,i}): on-policy imitation of
+                              * the optimal action at every visited state                               */
+typedef struct dpt_interactive_mdp_args {
+    int32_t N;              /* envs of this chunk                                            */
+    int32_t K;              /* steps: K forwards at windows 1 .. K, K - 1 transitions        */
+    int32_t dim;            /* room side, >= 1                                               */
+    int32_t loss_mode;      /* DPT_MDP_LOSS_*                                                */
+    int32_t flags;          /* DPT_INTERACTIVE_ACCUMULATE or 0                               */
+    int32_t sample;         /* 1: sampled actions (temp 1), 0: greedy                        */
+    int64_t first_task;     /* global id of env 0 of the chunk (Philox counter)              */
+    double scale;           /* LAST: 1 / (envs of the whole step); EVERY: 1 / (envs * K)     */
+    uint64_t seed;
+    uint64_t counter;       /* Philox counter of step 0                                      */
+    const int32_t* goal;    /* (N, 2) in [0, dim)                                            */
+    const int32_t* perm;    /* (N, 5) as dpt_darkroom_step takes it, or NULL                 */
+    const double* uniforms; /* (K - 1, N) or NULL -> Philox                                  */
+    int32_t* states_out;    /* (N, K, 2) s_0 .. s_{K-1}, always written                      */
+    int32_t* actions_out;   /* (N, K - 1)                                                    */
+    int32_t* rewards_out;   /* (N, K - 1)                                                    */
+    int32_t* targets_out;   /* (N, K) opt_action(s_t)                                        */
+    float* workspace;       /* dpt_interactive_mdp_workspace_numel floats, 16-byte aligned   */
+    float* dblob;           /* dpt_train_blob_numel floats (NULL with DPT_MDP_LOSS_NONE)     */
+    double* loss_acc;       /* += scale * the chunk's summed loss (NULL with LOSS_NONE)      */
+} dpt_interactive_mdp_args;
+
+/* floats of workspace for a chunk of N envs over K steps in `loss_mode`: the training workspace at window
+ * K (it serves every shorter window), tokens, logits, the int64 targets of the current step and, in a loss
+ * mode, dpreds, the chunk's gradient blob, the per-env losses and (EVERY) one step's gradient blob */
+int dpt_interactive_mdp_workspace_numel(const dpt_train_desc* desc_host, int32_t N, int32_t K, int32_t loss_mode,
+                                        int64_t* numel_out_host);
+/* One chunk of envs, one chain of launches on one stream: no host synchronisation, no allocation, no side
+ * streams, no graph capture.  For t = 0 .. K - 1: dpt_mdp_pack -> dpt_train_forward at window t + 1 (a
+ * loss-bearing step -- every step in EVERY, step K - 1 in LAST: a training forward with
+ * DPT_TRAIN_LAST_LOSS, dpt_train_ce_last against target_t with `scale`, dpt_train_backward, and the
+ * step's gradient added into the chunk's element-wise in step order; otherwise DPT_TRAIN_FORWARD_ONLY |
+ * DPT_TRAIN_LAST_ONLY) -> dpt_darkroom_act_step for t < K - 1.  With DPT_INTERACTIVE_ACCUMULATE the
+ * chunk's gradient is added to dblob, otherwise it replaces it (apply dpt_adamw_step after the last
+ * chunk).  desc: the model's n_layer, n_embd, state_dim, action_dim, n_positions (batch / window / flags
+ * are ignored).  Host checks fail before any launch: null pointers, N < 1, K < 1, K > n_positions, N * K
+ * above 2^26 rows, state_dim != 2 or action_dim != 5 (DPT_EUNSUPPORTED), dim < 1, dropout != 0, an unknown
+ * loss mode or flags, a workspace that is not 16-byte aligned, dblob or loss_acc NULL in a loss mode. */
+int dpt_interactive_mdp_grad(const dpt_train_desc* desc_host, const float* blob,
+                             const dpt_interactive_mdp_args* args_host, void* stream);
 
 /* ------------------------------------------------------------------ explorer/exploiter training step
  * One episode of train_explorer_exploiter.py:102-192 for two models of one config.  The explorer's
