@@ -63,6 +63,8 @@ int64_t darkroom_workspace_numel(int N, int64_t window);
 int prefill_max_window(const ModelView&);
 int launch_prefill(const ModelView&, const float*, const float*, const float*, const float*, const float*,
                    const float*, int, int, int, float*, hipStream_t);
+bool darkroom_episode_fits(int n_layer, int K);
+int launch_darkroom_episode(const ModelView&, const float*, const dpt_darkroom_episode_args&, hipStream_t);
 int set_decode_tile(int);
 int set_darkroom_memo(int);
 int set_cache_budget(int64_t);
@@ -348,6 +350,40 @@ int dpt_forward_window(const dpt_model* m, const float* query, const float* stat
     DPT_REQUIRE(workspace, "null workspace (needed for windows over %d tokens)", prefill_max_window(m->view));
     return launch_window_decode(m->view, workspace, N, C, query, states, actions, next_states, rewards, out_mode,
                                 out, as_stream(stream));
+}
+
+int dpt_rollout_darkroom_episode(const dpt_model* m, const dpt_darkroom_episode_args* a, void* stream) {
+    const char* who = "darkroom episode";
+    DPT_REQUIRE(m && a, "%s: null model / args", who);
+    DPT_REQUIRE(a->goal && a->states && a->targets, "%s: null goal / states / targets", who);
+    DPT_REQUIRE(a->N >= 1, "%s: N=%d", who, a->N);
+    DPT_REQUIRE(a->K >= 1, "%s: K=%d (at least 1)", who, a->K);
+    DPT_REQUIRE(a->K <= m->desc.n_positions, "%s: K=%d exceeds n_positions=%d", who, a->K, m->desc.n_positions);
+    DPT_REQUIRE(a->dim >= 1 && a->dim <= 255, "%s: dim=%d (1 .. 255: the records keep coordinates as bytes)", who,
+                a->dim);
+    DPT_REQUIRE(a->K == 1 || (a->actions && a->rewards), "%s: null actions / rewards with K=%d", who, a->K);
+    // the unsupported shapes from the desc alone: nothing below reads device state
+    const dpt_model_desc& d = m->desc;
+    if (d.state_dim != 2 || d.action_dim != 5) {
+        set_error(DPT_EUNSUPPORTED, "%s: state_dim=%d action_dim=%d (DarkRoom has state_dim 2, action_dim 5)", who,
+                  d.state_dim, d.action_dim);
+        return DPT_EUNSUPPORTED;
+    }
+    if (d.n_embd != kE) {
+        set_error(DPT_EUNSUPPORTED, "%s: n_embd=%d: only n_embd=%d is built", who, d.n_embd, kE);
+        return DPT_EUNSUPPORTED;
+    }
+    ModelView shape{};
+    shape.n_layer = d.n_layer;
+    shape.A = d.action_dim;
+    shape.F = 2 * d.state_dim + d.action_dim + 1;
+    const int wmax = prefill_max_window(shape);
+    if (a->K > wmax || !darkroom_episode_fits(d.n_layer, a->K)) {
+        set_error(DPT_EUNSUPPORTED, "%s: K=%d above the %d-token prefill window of this model, or its parameters and "
+                  "the episode's records do not fit in LDS (n_layer=%d)", who, a->K, wmax, d.n_layer);
+        return DPT_EUNSUPPORTED;
+    }
+    return launch_darkroom_episode(m->view, m->frag, *a, as_stream(stream));
 }
 
 int dpt_decode_step(const dpt_model* m, float* kv, int32_t N, int32_t max_pos, int32_t pos, const float* token,

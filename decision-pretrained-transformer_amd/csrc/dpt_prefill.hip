@@ -10,6 +10,10 @@
 // NW = 4, 8, 16 waves cover windows of 128, 256, 512 tokens (16 waves: K and V
 // of 512 tokens fill 140 KB of LDS, one workgroup per CU).  Longer windows go
 // to window_decode_kernel (dpt_decode.hip).
+//
+// The same forward inside a step loop is the in-episode DarkRoom rollout
+// (rollout_darkroom_episode_kernel, below): one launch runs a whole episode per env.
+#include "dpt_darkroom_env.h"
 #include "dpt_mfma_fwd.h"
 
 namespace dpt {
@@ -206,6 +210,304 @@ int launch_prefill(const ModelView& M, const float* frag, const float* q, const 
     if (T <= 128) return launch_nw<4>(M, a, dyn, st);
     if (T <= 256) return launch_nw<8>(M, a, dyn, st);
     return launch_nw<16>(M, a, dyn, st);
+}
+
+// ----------------------------------------------------------------------------- the episode rollout
+// The in-episode DarkRoom rollout (include/dpt_hip.h, dpt_rollout_darkroom_episode) in one launch: one
+// workgroup per env runs the K steps of the episode.  Step t embeds the window W_t (T = t + 1 tokens:
+// the query state s_t at position 0, then the episode's own t transitions) from the records the
+// workgroup keeps in LDS, runs prefill_kernel's forward over it (the same helpers in the same order, the
+// block count growing with t), reads the logits of position T - 1, and one thread selects, moves and
+// appends to the records.  The model's parameter block is loaded once per launch, not per step; the
+// records reach global memory once, after the last step.
+
+constexpr int kEpA = 5, kEpF = 10;  // DarkRoom: 5 actions, tokens [s (2) | onehot(a) (5) | s' (2) | r]
+constexpr int kEpGx = 0, kEpGy = 1, kEpRet = 2;  // EpLds::perm's tail
+
+struct EpisodeArgs {
+    int N, K, dim, sample;
+    int64_t first_task;
+    uint64_t seed, counter;
+    const int32_t *goal, *perm;
+    const double* uniforms;
+    int32_t *states, *actions, *rewards, *targets;
+    float* logits;
+    int32_t* returns;
+    const float* frag;
+};
+
+// The episode's LDS after the parameter block (byte offsets from P + PfTop::total, 16-byte aligned
+// regions): the selection uniforms, the step's logits, the permutation with the goal and the return so
+// far, the env's output pointers, and the records as bytes (coordinates below dim <= 255, actions below 5,
+// rewards 0 / 1): 5 K bytes of records, 8 K of uniforms.
+struct EpLds {
+    int u, lg, perm, out, st, act, rew, tgt, total;
+    __host__ __device__ static EpLds make(int K) {
+        EpLds e;
+        const int k16 = (K + 15) & ~15;
+        int o = 0;
+        e.u = o; o += 8 * k16;
+        e.lg = o; o += 32;
+        e.perm = o; o += 32;  // perm (5), then goal x, goal y, return
+        e.out = o; o += 48;   // the five output pointers of this env (read back after the last step)
+        e.st = o; o += 2 * k16;
+        e.act = o; o += k16;
+        e.rew = o; o += k16;
+        e.tgt = o; o += k16;
+        e.total = o;
+        return e;
+    }
+};
+
+template <int NW>
+__global__ void __launch_bounds__(NW * 64, (NW + 3) / 4)
+rollout_darkroom_episode_kernel(ModelView M, EpisodeArgs a) {
+    __shared__ KVBuf<32 * NW> S;
+    extern __shared__ float P[];
+    const int n = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = M.n_layer, K = a.K;
+    const float scale = 0.17677669529663687f;  // 1/sqrt(head_dim = 32)
+    const PfTop pt = PfTop::make(L, kEpF, kEpA);
+    const EpLds el = EpLds::make(K);
+    unsigned char* R = reinterpret_cast<unsigned char*>(P + pt.total);
+    double* u_ep = reinterpret_cast<double*>(R + el.u);
+    float* lg_s = reinterpret_cast<float*>(R + el.lg);
+    int32_t* perm_s = reinterpret_cast<int32_t*>(R + el.perm);
+    int32_t* env_s = perm_s + kEpA;  // goal x, goal y, the return so far
+    int32_t** out_s = reinterpret_cast<int32_t**>(R + el.out);
+    unsigned char *st = R + el.st, *ac = R + el.act, *rw = R + el.rew, *tg = R + el.tgt;
+    const FragSrc3 split0{__builtin_amdgcn_make_buffer_rsrc((void*)a.frag, (short)0, L * Frag3::bytes, 0x00020000), 0};
+    load_layer_params(P, M, tid, blockDim.x);
+    for (int i = tid; i < kE; i += blockDim.x) {
+        P[pt.lnf_g + i] = M.lnf_g[i];
+        P[pt.lnf_b + i] = M.lnf_b[i];
+        P[pt.emb_b + i] = M.emb_b[i];
+    }
+    for (int i = tid; i < kE * kEpA; i += blockDim.x) P[pt.head_w + (i % kEpA) * kE + i / kEpA] = M.head_w[i];
+    for (int i = tid; i < kEpA; i += blockDim.x) P[pt.head_b + i] = M.head_b[i];
+    for (int i = tid; i < kEpF * kE; i += blockDim.x) P[pt.emb_w + i] = M.emb_w[i];
+    // the env: permutation, goal, s_0 = (0, 0) and its expert action.  What only the selecting thread
+    // or the epilogue reads (goal, return, output pointers) waits in LDS, not in registers held across
+    // the step loop.
+    if (tid < kEpA) perm_s[tid] = a.perm ? a.perm[(size_t)n * kEpA + tid] : tid;
+    // the episode's selection uniforms up front, one thread per step (off the serial select chain)
+    if (a.sample)
+        for (int t = tid; t < K - 1; t += blockDim.x)
+            u_ep[t] = a.uniforms ? a.uniforms[(size_t)t * a.N + n]
+                                 : philox_uniform(a.seed, a.counter + (uint64_t)t, a.first_task + n, DPT_STREAM_SELECT);
+    if (tid == 0) {
+        const int gx = a.goal[2 * (size_t)n], gy = a.goal[2 * (size_t)n + 1];
+        env_s[kEpGx] = gx;
+        env_s[kEpGy] = gy;
+        env_s[kEpRet] = 0;
+        st[0] = 0;
+        st[1] = 0;
+        tg[0] = (unsigned char)darkroom_opt(0, 0, gx, gy, a.perm ? a.perm + (size_t)n * kEpA : nullptr);
+        out_s[0] = a.states + (size_t)n * 2 * K;
+        out_s[1] = a.actions + (size_t)n * (K - 1);
+        out_s[2] = a.rewards + (size_t)n * (K - 1);
+        out_s[3] = a.targets + (size_t)n * K;
+        out_s[4] = a.returns ? a.returns + n : nullptr;
+    }
+    __syncthreads();
+
+    for (int t = 0; t < K; ++t) {
+        // The wave's blocks of this step from copies the compiler cannot see through: the block
+        // assignment changes with the window, and values derived from a hoistable wave index would be
+        // kept across the whole step loop in scalar registers that spill.
+        int wv = wave;
+        asm volatile("" : "+s"(wv));
+        const int T = t + 1;
+        const int nqb = (T + 15) >> 4;
+        int qb[2];
+        const int nb = blocks_of_wave(wv, nqb, qb);
+
+        // embeddings of W_t from the records: token 0 = [s_t, 0_A, 0_sd, 0], token 1 + j =
+        // [s_j, onehot(a_j), s_{j+1}, r_j] (prefill_kernel's accumulation order over the 10 features)
+        float x[2][8];
+        {
+            const int lane = lane_id(), g = lane >> 4;
+            // a zero made in this step: a constant's register is hoisted out of the step loop and kept
+            // (spilled) across the layers
+            float zero = 0.f;
+            asm volatile("" : "+v"(zero));
+            const __amdgpu_buffer_rsrc_t wpe_r =
+                __builtin_amdgcn_make_buffer_rsrc((void*)M.wpe, (short)0, K * kE * (int)sizeof(float), 0x00020000);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) x[j][k] = zero;
+                const int tok = qb[j] * 16 + (lane & 15);
+                if (j >= nb || tok >= T) continue;
+                const int sj = tok == 0 ? T - 1 : tok - 1;
+                float v[kEpF];
+#pragma unroll
+                for (int f = 0; f < kEpF; ++f) v[f] = zero;
+                v[0] = (float)st[2 * sj];
+                v[1] = (float)st[2 * sj + 1];
+                if (tok > 0) {
+                    const int aj = ac[sj];
+#pragma unroll
+                    for (int k = 0; k < kEpA; ++k) v[2 + k] = aj == k ? 1.f : zero;
+                    v[2 + kEpA] = (float)st[2 * tok];
+                    v[3 + kEpA] = (float)st[2 * tok + 1];
+                    v[4 + kEpA] = (float)rw[sj];
+                }
+                floatx4 acc0 = ld4(P + pt.emb_b + 4 * g), acc1 = ld4(P + pt.emb_b + 16 + 4 * g);
+#pragma unroll
+                for (int f = 0; f < kEpF; ++f) {
+                    const floatx4 w0 = ld4(P + pt.emb_w + f * kE + 4 * g), w1 = ld4(P + pt.emb_w + f * kE + 16 + 4 * g);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        acc0[r] = fmaf(v[f], w0[r], acc0[r]);
+                        acc1[r] = fmaf(v[f], w1[r], acc1[r]);
+                    }
+                }
+                // (buffer loads at a 32-bit byte offset: a 64-bit per-lane address takes a zero half, a
+                // constant register that is hoisted out of the step loop and spilled across the layers)
+                const int po = (tok * kE + 4 * g) * 4;
+                const floatx4 p0 = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(wpe_r, po, 0, 0));
+                const floatx4 p1 = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(wpe_r, po + 64, 0, 0));
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    x[j][r] = acc0[r] + p0[r];
+                    x[j][4 + r] = acc1[r] + p1[r];
+                }
+            }
+        }
+
+        for (int layer = 0; layer < L; ++layer) {
+            const float* W = P + layer * PL::size;
+            const FragSrc3 fs = split0.layer(layer);
+            float q[2][8];
+            {
+                float xn[2][8];
+                DPT_BLOCKS(nb, (ln_n<NB>(x, xn, W + PL::ln1_g, W + PL::ln1_b), u_proj3_n<NB>(W, fs, xn, q, M),
+                                kv_from_y<NB>(S, qb, xn, M)));
+            }
+            bar_lds();
+            if (nb > 0) {
+                float o[2][8], l[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    if (j >= nb) break;
+                    float m;
+                    attend(S, q[j], qb[j], 0, scale, m, l[j], o[j], M);
+                }
+                DPT_BLOCKS(nb, attn_proj3_ol<NB>(W, fs, o, l, x, M));
+            }
+            bar_lds();  // every read of this layer's K/V is done
+            {
+                // the MLP's scales through copies made in this layer: the gelu constants derived from
+                // them are otherwise computed once per launch and held in four registers across the
+                // attention of every layer and step (a few scalar and vector instructions per layer)
+                int ew = M.mlp_ew, ex = M.mlp_ex;
+                asm volatile("" : "+s"(ew), "+s"(ex));
+                float xn[2][8];
+                DPT_BLOCKS(nb, (ln_n<NB>(x, xn, W + PL::ln2_g, W + PL::ln2_b), mlp3_n<NB>(W, fs, xn, x, ew, ex)));
+            }
+        }
+
+        // ln_f + pred_actions of position T - 1, by the wave that owns its block
+        {
+            const int lane = lane_id(), g = lane >> 4, c = lane & 15;
+            const int qlast = (T - 1) >> 4, clast = (T - 1) & 15;
+            // the logits row's offset through a zero made here: the compiler otherwise addresses the
+            // stores with the zero register of x's initial value, kept (spilled) across the layers
+            int z0 = 0;
+            asm volatile("" : "+v"(z0));
+            float* lg_out = a.logits ? a.logits + ((size_t)n * K + (T - 1)) * kEpA + z0 : nullptr;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                if (j >= nb || qb[j] != qlast) continue;  // wave-uniform
+                float xf[8];
+                ln_cols(x[j], xf, P + pt.lnf_g, P + pt.lnf_b);
+#pragma unroll
+                for (int act = 0; act < kEpA; ++act) {
+                    const floatx4 w0 = ld4(P + pt.head_w + act * kE + 4 * g);
+                    const floatx4 w1 = ld4(P + pt.head_w + act * kE + 16 + 4 * g);
+                    float part = 0.f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        part = fmaf(xf[r], w0[r], part);
+                        part = fmaf(xf[4 + r], w1[r], part);
+                    }
+                    const float lg = sum_cols(part) + P[pt.head_b + act];
+                    if (g == 0 && c == clast) {
+                        lg_s[act] = lg;
+                        if (lg_out) lg_out[act] = lg;
+                    }
+                }
+            }
+        }
+        bar_lds();
+        // one thread: dpt_select_action's rule (mdp_act_kernel's call), the move, the reward and the next
+        // expert action, appended to the records.  The K-th action is never drawn.
+        if (tid == 0 && T < K) {
+            float lg[kEpA];
+#pragma unroll
+            for (int k = 0; k < kEpA; ++k) lg[k] = lg_s[k];
+            const double u = a.sample ? u_ep[T - 1] : 0.0;
+            const int act = select_fixed_fast<kEpA>(lg, a.sample, 1.0f, u);
+            const int32_t* pm = a.perm ? perm_s : nullptr;
+            int cur_x = st[2 * (T - 1)], cur_y = st[2 * (T - 1) + 1];
+            const int gx = env_s[kEpGx], gy = env_s[kEpGy];
+            darkroom_move(cur_x, cur_y, pm ? pm[act] : act, a.dim);
+            const int r = (cur_x == gx && cur_y == gy) ? 1 : 0;
+            env_s[kEpRet] += r;
+            ac[T - 1] = (unsigned char)act;
+            rw[T - 1] = (unsigned char)r;
+            st[2 * T] = (unsigned char)cur_x;
+            st[2 * T + 1] = (unsigned char)cur_y;
+            tg[T] = (unsigned char)darkroom_opt(cur_x, cur_y, gx, gy, pm);
+        }
+        bar_lds();
+    }
+
+    // the records, once (the loop's last barrier ordered them)
+    int32_t *o_st = out_s[0], *o_ac = out_s[1], *o_rw = out_s[2], *o_tg = out_s[3], *o_ret = out_s[4];
+    for (int i = tid; i < 2 * K; i += blockDim.x) o_st[i] = st[i];
+    for (int i = tid; i < K - 1; i += blockDim.x) {
+        o_ac[i] = ac[i];
+        o_rw[i] = rw[i];
+    }
+    for (int i = tid; i < K; i += blockDim.x) o_tg[i] = tg[i];
+    if (tid == 0 && o_ret) *o_ret = env_s[kEpRet];
+}
+
+template <int NW>
+static int launch_episode_nw(const ModelView& M, const EpisodeArgs& a, size_t dyn, hipStream_t st) {
+    if (!prefill_fits(dyn, 32 * NW)) {
+        set_error(DPT_EUNSUPPORTED, "darkroom episode: parameter block and records (%zu bytes) do not fit in LDS", dyn);
+        return DPT_EUNSUPPORTED;
+    }
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_darkroom_episode_kernel<NW>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    hipLaunchKernelGGL(rollout_darkroom_episode_kernel<NW>, dim3(a.N), dim3(NW * 64), dyn, st, M, a);
+    return check_hip(hipGetLastError(), "rollout_darkroom_episode_kernel launch");
+}
+
+// Bytes of dynamic LDS of an episode of K steps for a model of n_layer blocks, and whether they fit
+// next to the K/V buffer of the geometry K runs on (a host-only test: dpt_rollout_darkroom_episode's
+// unsupported-shape check, made before any launch).
+static size_t episode_dyn_bytes(int n_layer, int K) {
+    return sizeof(float) * (size_t)PfTop::make(n_layer, kEpF, kEpA).total + (size_t)EpLds::make(K).total;
+}
+bool darkroom_episode_fits(int n_layer, int K) {
+    if (K > kPrefillMaxT) return false;
+    return prefill_fits(episode_dyn_bytes(n_layer, K), K <= 128 ? 128 : K <= 256 ? 256 : 512);
+}
+
+int launch_darkroom_episode(const ModelView& M, const float* frag, const dpt_darkroom_episode_args& h,
+                            hipStream_t st) {
+    EpisodeArgs a{h.N,     h.K,      h.dim,     h.sample,  h.first_task, h.seed,   h.counter, h.goal, h.perm,
+                  h.uniforms, h.states, h.actions, h.rewards, h.targets,    h.logits, h.returns, frag};
+    const size_t dyn = episode_dyn_bytes(M.n_layer, h.K);
+    if (h.K <= 128) return launch_episode_nw<4>(M, a, dyn, st);
+    if (h.K <= 256) return launch_episode_nw<8>(M, a, dyn, st);
+    return launch_episode_nw<16>(M, a, dyn, st);
 }
 
 }  // namespace dpt

@@ -361,6 +361,50 @@ def rollin_darkroom(goals, H, dim=10, perm=None, mode=0, states=None, actions=No
     return out
 
 
+# ----------------------------------------------------------------------------- in-episode DarkRoom rollout
+
+def rollout_darkroom_episode(model, goals, K, dim, sample=True, perm=None, uniforms=None, seed=None, first_task=0,
+                             logits=False):
+    """The in-episode DarkRoom rollout in one launch (dpt_rollout_darkroom_episode): every env runs its K
+    steps from s_0 = (0, 0) in one workgroup, the context being the episode's own transitions and the
+    query state sitting at position 0.  ``model``: a width-32 ``models.net.Transformer`` with state_dim 2
+    and action_dim 5 (its ``device_model()`` runs).  ``goals`` (N, 2) in [0, dim), ``perm`` (N, 5) the
+    action permutations dpt_darkroom_step takes, ``uniforms`` (K - 1, N) inject the selection uniforms;
+    otherwise Philox keyed by ``seed`` (default ``next_seed()``) and the env's global index
+    ``first_task + i``.  Returns (records, returns[, logits]): the records dict of
+    ``dpt_hip.train.rollout_darkroom_interactive`` (int32 device tensors states (N, K, 2), actions
+    (N, K - 1), rewards (N, K - 1), targets (N, K)), the per-env return (N) int64, and with ``logits`` the
+    (N, K, 5) fp32 logits every step selected from.  Raises NotImplementedError for other widths and for K
+    above the model's prefill window (use ``rollout_darkroom_interactive``)."""
+    from .train import _mdp_check_model, _mdp_episode
+    who = "rollout_darkroom_episode"
+    _mdp_check_model(model, who)
+    if model.dropout > 0 and model.training:
+        raise ValueError(f"{who}: the model is in training mode with dropout > 0 (call model.eval(): the rollout's "
+                         f"forwards have no dropout masks)")
+    dm = model.device_model()  # NotImplementedError at other widths
+    dev, K = device(), int(K)
+    g, pm, u, seed = _mdp_episode(goals, K, perm, uniforms, seed, dev)
+    N = int(g.shape[0])
+    rec = dict(states=torch.empty((N, K, 2), dtype=torch.int32, device=dev),
+               actions=torch.empty((N, K - 1), dtype=torch.int32, device=dev),
+               rewards=torch.empty((N, K - 1), dtype=torch.int32, device=dev),
+               targets=torch.empty((N, K), dtype=torch.int32, device=dev))
+    ret = torch.empty(N, dtype=torch.int32, device=dev)
+    lg = torch.empty((N, K, 5), dtype=torch.float32, device=dev) if logits else None
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    args = _lib.DarkroomEpisodeArgs(
+        N, K, int(dim), int(bool(sample)), int(first_task), seed, 0, ptr(g), ptr(pm), ptr(u), ptr(rec["states"]),
+        ptr(rec["actions"]) if K > 1 else None, ptr(rec["rewards"]) if K > 1 else None, ptr(rec["targets"]), ptr(lg),
+        ptr(ret))
+    _lib.call("dpt_rollout_darkroom_episode", dm.handle, ctypes.byref(args), _stream())
+    out = (rec, ret.to(torch.int64))
+    return out + (lg,) if logits else out
+
+
 # ----------------------------------------------------------------------------- classical baselines
 
 from ._lib import (POLICY_EMP, POLICY_LCB, POLICY_LINUCB, POLICY_OPT, POLICY_THOMPSON,  # noqa: E402,F401

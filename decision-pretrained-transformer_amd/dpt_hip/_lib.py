@@ -277,6 +277,17 @@ SIGNATURES["dpt_interactive_mdp_grad"] = (_i32, [_train_desc_p, _c_void_p, ctype
                                                  _c_void_p])
 
 
+class DarkroomEpisodeArgs(ctypes.Structure):
+    """dpt_darkroom_episode_args: the in-episode DarkRoom rollout of N envs over K steps in one launch."""
+    _fields_ = [("N", _i32), ("K", _i32), ("dim", _i32), ("sample", _i32), ("first_task", _i64), ("seed", _u64),
+                ("counter", _u64), ("goal", _c_void_p), ("perm", _c_void_p), ("uniforms", _c_void_p),
+                ("states", _c_void_p), ("actions", _c_void_p), ("rewards", _c_void_p), ("targets", _c_void_p),
+                ("logits", _c_void_p), ("returns", _c_void_p)]
+
+
+SIGNATURES["dpt_rollout_darkroom_episode"] = (_i32, [_c_void_p, ctypes.POINTER(DarkroomEpisodeArgs), _c_void_p])
+
+
 EXPLORE_ACCUMULATE = 1  # dpt_explore_args.flags: both dblobs += the chunk's gradients
 
 

@@ -51,7 +51,8 @@ extern "C" {
  * dpt_image_act_workspace_numel, dpt_image_act_set_context, dpt_image_act_step); the explore-then-exploit
  * evaluation (dpt_recommend_curve, dpt_empirical_recommend, dpt_exploit_eval_workspace_numel,
  * dpt_exploit_eval); the interactive DarkRoom training step (dpt_mdp_pack, dpt_darkroom_act_step,
- * dpt_interactive_mdp_workspace_numel, dpt_interactive_mdp_grad) */
+ * dpt_interactive_mdp_workspace_numel, dpt_interactive_mdp_grad); the in-episode DarkRoom rollout in one
+ * launch (dpt_rollout_darkroom_episode) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -689,6 +690,43 @@ int dpt_interactive_mdp_workspace_numel(const dpt_train_desc* desc_host, int32_t
  * loss mode or flags, a workspace that is not 16-byte aligned, dblob or loss_acc NULL in a loss mode. */
 int dpt_interactive_mdp_grad(const dpt_train_desc* desc_host, const float* blob,
                              const dpt_interactive_mdp_args* args_host, void* stream);
+
+/* ------------------------------------------------------------------ in-episode DarkRoom rollout, one launch
+ * The episode of the section above without a loss, for a width-32 dpt_model: one workgroup per env runs
+ * all K steps in one kernel.  The model's parameters are loaded into LDS once per launch, the episode's
+ * records live in LDS, and each step's window W_t is embedded from them and run through the MFMA forward
+ * of dpt_forward_window's prefill; the logits of position t select a_t by dpt_select_action's rule at
+ * temp 1 (uniforms[t][i], or Philox(seed, (counter + t, first_task + i, DPT_STREAM_SELECT)); greedy: the
+ * first argmax), then dpt_darkroom_step's move and dpt_darkroom_opt_action's label.  The records are
+ * those of dpt_interactive_mdp_grad; the logits are the prefill's (fp32, within the reference logit
+ * bound of the float64 forward), not the training forward's, so a draw whose uniform lies within that
+ * bound of a cdf edge may fall differently in the two.  No workspace, no allocation, no host
+ * synchronisation.  ABI 8, additive. */
+typedef struct dpt_darkroom_episode_args {
+    int32_t N;              /* envs                                                          */
+    int32_t K;              /* steps: K forwards at windows 1 .. K, K - 1 transitions        */
+    int32_t dim;            /* room side, 1 .. 255                                           */
+    int32_t sample;         /* nonzero: sampled actions (temp 1), 0: greedy                  */
+    int64_t first_task;     /* global id of env 0 (Philox counter)                           */
+    uint64_t seed;
+    uint64_t counter;       /* Philox counter of step 0                                      */
+    const int32_t* goal;    /* (N, 2) in [0, dim)                                            */
+    const int32_t* perm;    /* (N, 5) as dpt_darkroom_step takes it, or NULL                 */
+    const double* uniforms; /* (K - 1, N) or NULL -> Philox                                  */
+    int32_t* states;        /* (N, K, 2) s_0 .. s_{K-1}                                      */
+    int32_t* actions;       /* (N, K - 1) (may be NULL when K = 1)                           */
+    int32_t* rewards;       /* (N, K - 1) (may be NULL when K = 1)                           */
+    int32_t* targets;       /* (N, K) opt_action(s_t)                                        */
+    float* logits;          /* (N, K, 5) the logits every step selected from, or NULL        */
+    int32_t* returns;       /* (N) the sum of the K - 1 rewards, or NULL                     */
+} dpt_darkroom_episode_args;
+
+/* Host checks fail before any launch.  DPT_EINVAL: null model, args, goal, states or targets; N < 1;
+ * K < 1; K > n_positions; dim < 1 or dim > 255; actions or rewards NULL while K > 1.  DPT_EUNSUPPORTED:
+ * state_dim != 2 or action_dim != 5; n_embd != 32; K above dpt_forward_window's prefill limit for the model
+ * (512 tokens at most), or a model so deep that its parameter block and the episode's records do not fit
+ * in LDS next to the keys and values of K tokens. */
+int dpt_rollout_darkroom_episode(const dpt_model* model, const dpt_darkroom_episode_args* args_host, void* stream);
 
 /* ------------------------------------------------------------------ explorer/exploiter training step
  * One episode of train_explorer_exploiter.py:102-192 for two models of one config.  The explorer's

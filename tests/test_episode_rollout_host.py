@@ -1,0 +1,236 @@
+"""CPU checks of the episode rollout (csrc/dpt_prefill.hip rollout_darkroom_episode_kernel,
+dpt_rollout_darkroom_episode) and of evals/eval_interactive_darkroom.py: the oracle margins of every case
+the GPU file compares (a float64 forward cannot tell which way a draw at a cdf edge falls), the entry
+point's host checks with no device present, its ctypes signature and struct layout against the header,
+the tool's statistics on hand-made records, and its flags.  No device work is launched."""
+import ctypes
+import importlib
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import episode_rollout_cases as EC
+import interactive_mdp_oracle as MO
+from conftest import ROOT
+from test_abi import HEADER
+from test_isa_hazards import HIPCC
+from test_resource_budget import remarks
+
+NAME = "dpt_rollout_darkroom_episode"
+
+
+# ----------------------------------------------------------------------------- the compared cases
+@pytest.mark.parametrize("name", list(EC.TABLE))
+def test_table_cases_are_clear_of_near_ties(name):
+    """every draw (greedy: every argmax gap) of the oracle's episode has a margin above 1e-5, the bar on the
+    device's logits; the case is the issue's (model seed 2000 + K, RandomState(0): goals first, uniforms second)"""
+    K, N, dim, sample = EC.TABLE[name]
+    m, goals, u, sampled, d, L, ep = EC.table_case(name)
+    assert (sampled, d, L) == (sample, dim, 4) and goals.shape == (N, 2) and u.shape == (K - 1, N)
+    assert m.n_embd == 32 and m.n_layer == 4 and m.n_positions >= K
+    rs = np.random.RandomState(0)
+    assert np.array_equal(goals, rs.randint(0, dim, (N, 2))) and np.array_equal(u, rs.uniform(size=(K - 1, N)))
+    assert ep["margins"].shape == (K - 1, N)
+    assert ep["logits"].shape == (K, N, 5) and np.isfinite(ep["logits"]).all()
+    if K > 1:
+        print(f"{name}: min margin {ep['margins'].min():.3e}")
+        assert ep["margins"].min() > EC.MARGIN, ep["margins"].min()
+    assert (ep["states"][:, 0] == 0).all()
+    assert (ep["targets"] == np.stack([MO.opt_action(ep["states"][:, t], goals) for t in range(K)], 1)).all()
+
+
+def test_the_long_cases_reach_their_goals_and_cross_every_geometry():
+    """the table's windows cross 16, 32, 128 and 256 tokens, and some long episode collects a reward (the
+    reward feature and the stay-at-goal branch are exercised)"""
+    ks = sorted(k for k, _, _, _ in EC.TABLE.values())
+    for edge in (1, 16, 32, 128, 256):
+        assert any(k > edge for k in ks) and any(k <= edge for k in ks)
+    assert max(ks) <= 512
+    assert any(EC.table_case(n)[-1]["rewards"].any() for n in ("K17", "K129", "K257"))
+
+
+@pytest.mark.parametrize("permuted", [False, True])
+def test_records_case_margins(permuted):
+    ep = EC.records_case(permuted)[6]
+    assert ep["margins"].min() > EC.MARGIN
+    if permuted:  # the control the GPU file relies on: dropping the permutation changes the oracle's records
+        ctl = EC.unpermuted_control()
+        assert any(not np.array_equal(ctl[k], ep[k]) for k in ("states", "actions", "rewards", "targets"))
+        assert not np.array_equal(np.roll(ep["targets"], 1, axis=1), ep["targets"])
+
+
+def test_sharp_case_margins_and_sharpness():
+    import sharp_models
+    _, w64, _, _, _, _, L, ep = EC.sharp_case()
+    assert ep["margins"].min() > EC.MARGIN, ep["margins"].min()
+    tok = MO.window(ep["states"], ep["actions"], ep["rewards"], 16).numpy()
+    sharp_models.assert_sharp(EC.SHARP_LEVEL, sharp_models.token_stats(w64, L, tok), "episode rollout")
+
+
+# ----------------------------------------------------------------------------- the entry point on the host
+def test_signature_and_struct_match_the_header(tmp_path):
+    from dpt_hip import _lib
+    lib = _lib.load()
+    assert lib.dpt_abi_version() == 8 == _lib.ABI_VERSION
+    assert hasattr(lib, NAME) and NAME in _lib.SIGNATURES
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    proto = re.search(r"int\s+" + NAME + r"\s*\(([^)]*)\)", src).group(1)
+    params = [p.strip() for p in proto.split(",")]
+    assert params == ["const dpt_model* model", "const dpt_darkroom_episode_args* args_host", "void* stream"]
+    restype, argtypes = _lib.SIGNATURES[NAME]
+    assert restype is ctypes.c_int32 or restype is ctypes.c_int
+    assert argtypes == [ctypes.c_void_p, ctypes.POINTER(_lib.DarkroomEpisodeArgs), ctypes.c_void_p]
+    cls, cname = _lib.DarkroomEpisodeArgs, "dpt_darkroom_episode_args"
+    assert [f for f, _ in cls._fields_] == ["N", "K", "dim", "sample", "first_task", "seed", "counter", "goal", "perm",
+                                            "uniforms", "states", "actions", "rewards", "targets", "logits", "returns"]
+    cc = shutil.which("gcc") or shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler")
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "dpt_hip.h"', 'int main(void) {',
+             f'printf("size %zu\\n", sizeof({cname}));']
+    lines += [f'printf("{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
+    lines.append("return 0; }")
+    (tmp_path / "layout.c").write_text("\n".join(lines))
+    subprocess.run([cc, "-I", ROOT + "/include", str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
+    got = dict(line.rsplit(" ", 1) for line in subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True,
+                                                              text=True).stdout.splitlines())
+    assert int(got["size"]) == ctypes.sizeof(cls)
+    for f, _ in cls._fields_:
+        assert int(got[f]) == getattr(cls, f).offset, f
+
+
+def test_host_validation_without_a_device():
+    """Every check of dpt_rollout_darkroom_episode fails on the host before any launch.  A dpt_model begins
+    with its dpt_model_desc, and the checks read nothing else of it, so a zeroed host buffer with a desc in
+    front stands in for a model (a launch would fault on it: none is reached); the array pointers are host
+    memory too."""
+    from dpt_hip import _lib
+    lib = _lib.load()
+    buf = (ctypes.c_double * 64)()
+    p = ctypes.addressof(buf)
+
+    def model(L=2, E=32, sd=2, A=5, npos=2400):
+        mem = (ctypes.c_char * 4096)()
+        ctypes.memmove(mem, ctypes.byref(_lib.ModelDesc(L, E, sd, A, npos)), ctypes.sizeof(_lib.ModelDesc))
+        return mem
+
+    def call(m, **over):
+        f = dict(N=4, K=6, dim=3, sample=1, first_task=0, seed=1, counter=0, goal=p, perm=None, uniforms=None,
+                 states=p, actions=p, rewards=p, targets=p, logits=None, returns=None)
+        f.update(over)
+        a = _lib.DarkroomEpisodeArgs(*(f[k] for k, _ in _lib.DarkroomEpisodeArgs._fields_))
+        return lambda: _lib.check(getattr(lib, NAME)(ctypes.byref(m) if m is not None else None, ctypes.byref(a), None))
+
+    ok = model()
+    invalid = {
+        "null model": call(None),
+        "null args": lambda: _lib.check(getattr(lib, NAME)(ctypes.byref(ok), None, None)),
+        "null goal": call(ok, goal=None),
+        "null states": call(ok, states=None),
+        "null targets": call(ok, targets=None),
+        "null actions": call(ok, actions=None),
+        "null rewards": call(ok, rewards=None),
+        "N < 1": call(ok, N=0),
+        "K < 1": call(ok, K=0),
+        "K > n_positions": call(model(npos=5), K=6),
+        "dim < 1": call(ok, dim=0),
+        "dim > 255": call(ok, dim=256),
+    }
+    for name, fn in invalid.items():
+        with pytest.raises(ValueError):
+            fn()
+        assert lib.dpt_last_error(), name
+    for name, word in (("K > n_positions", "n_positions"), ("dim > 255", "dim"), ("N < 1", "N=0"), ("K < 1", "K=0")):
+        with pytest.raises(ValueError, match=word):
+            invalid[name]()
+    unsupported = {
+        "state_dim": call(model(sd=1)),
+        "action_dim": call(model(A=4)),
+        "n_embd": call(model(E=18)),
+        "K over the prefill window": call(ok, K=513),
+        # 40 layers of parameters fit next to the keys and values of 256 tokens, not of 512
+        "K over a deep model's window": call(model(L=40), K=257),
+        # 15 layers: the prefill takes 512 tokens, but the episode's 6.6 KB of records no longer fit beside them
+        "records do not fit": call(model(L=15), K=512),
+    }
+    for name, fn in unsupported.items():
+        with pytest.raises(NotImplementedError):
+            fn()
+        assert lib.dpt_last_error(), name
+    with pytest.raises(NotImplementedError, match="state_dim"):
+        unsupported["state_dim"]()
+    with pytest.raises(NotImplementedError, match="n_embd"):
+        unsupported["n_embd"]()
+    with pytest.raises(NotImplementedError, match="K=513"):
+        unsupported["K over the prefill window"]()
+    # K = 1 needs neither actions nor rewards: with both NULL the checks pass up to N, which stops the call
+    with pytest.raises(ValueError, match="N=0"):
+        call(ok, K=1, N=0, actions=None, rewards=None)()
+
+
+def test_python_entry_point_and_sources():
+    import dpt_hip
+    assert callable(dpt_hip.rollout_darkroom_episode)
+    src = open(ROOT + "/decision-pretrained-transformer_amd/csrc/dpt_prefill.hip").read()
+    assert "rollout_darkroom_episode_kernel" in src and "select_fixed_fast<kEpA>" in src
+    assert "darkroom_move(" in src and "darkroom_opt(" in src and "hipMalloc" not in src
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_episode_kernels_spill_no_more_than_their_prefill_kernels(tmp_path):
+    """the scratch bar: the kernel restates prefill_kernel<NW>'s loop body, so each instantiation uses no more
+    scratch bytes per lane than prefill_kernel of the same NW (more would be the step loop costing registers),
+    and keeps its occupancy"""
+    r = remarks("dpt_prefill.hip", tmp_path)
+    for nw in (4, 8, 16):
+        pf = [v for n, v in r.items() if f"prefill_kernelILi{nw}E" in n]
+        ep = [v for n, v in r.items() if f"rollout_darkroom_episode_kernelILi{nw}E" in n]
+        assert len(pf) == 1 and len(ep) == 1, list(r)
+        print(f"NW={nw}: prefill {pf[0]}, episode {ep[0]}")
+        assert ep[0]["scratch"] <= pf[0]["scratch"], (nw, ep[0], pf[0])
+        assert ep[0]["occ"] >= pf[0]["occ"], (nw, ep[0], pf[0])
+
+
+# ----------------------------------------------------------------------------- the tool
+def test_episode_stats_on_hand_made_records():
+    tool = importlib.import_module("evals.eval_interactive_darkroom")
+    #          step: 0  1  2  3
+    r = np.array([[0, 1, 1, 1],    # reached at step 1
+                  [0, 0, 0, 0],    # never
+                  [1, 1, 1, 1],    # at the goal from the first move
+                  [0, 0, 0, 1]])   # at the last step
+    acts = np.array([[0, 2, 4, 4], [1, 1, 1, 1], [4, 4, 4, 4], [0, 0, 2, 2]])
+    tgts = np.array([[0, 2, 4, 4, 4], [0, 0, 0, 0, 0], [4, 4, 4, 4, 4], [0, 0, 2, 3, 4]])
+    st = tool.episode_stats(r, acts, tgts)
+    assert st["reward_mean"].tolist() == [0.25, 0.5, 0.5, 0.75]
+    assert st["return_mean"].tolist() == [0.25, 0.75, 1.25, 2.0]
+    assert st["final_return"] == 2.0 and st["reached"] == 0.75
+    assert st["first_hit"] == (1 + 4 + 0 + 3) / 4  # K - 1 = 4 where the goal was never reached
+    assert st["agreement"] == (4 + 0 + 4 + 3) / 16
+    cum = np.cumsum(r, 1).astype(np.float64)
+    assert np.allclose(st["return_sem"], cum.std(0, ddof=1) / 2.0) and np.allclose(st["reward_sem"], r.std(0, ddof=1) / 2.0)
+    import scipy.stats
+    assert np.allclose(st["return_sem"], scipy.stats.sem(cum, axis=0))
+    one = tool.episode_stats(r[:1])
+    assert one["return_sem"].tolist() == [0.0] * 4 and "agreement" not in one
+    none = tool.episode_stats(np.zeros((3, 0)), np.zeros((3, 0), int), np.zeros((3, 1), int))  # K = 1
+    assert none["final_return"] == 0.0 and none["reached"] == 0.0 and none["first_hit"] == 0.0
+    assert none["reward_mean"].shape == (0,) and np.isnan(none["agreement"])
+
+
+def test_tool_flags():
+    tool = importlib.import_module("evals.eval_interactive_darkroom")
+    a = tool.parse_args([])
+    assert (a["n_eval"], a["seed"], a["model_path"], a["sample"], a["K"], a["save"], a["baseline_path"]) == (
+        100, 0, "trained_models/interactive_darkroom.pt", False, -1, "figs/eval_interactive_darkroom", None)
+    assert (a["H"], a["dim"], a["embd"], a["layer"], a["head"], a["dropout"], a["env"]) == (100, 10, 32, 3, 1, 0, "darkroom")
+    a = tool.parse_args(["--K", "12", "--sample", "--baseline_path", "b.pt", "--n_eval", "8", "--seed", "4", "--dim", "4",
+                         "--save", "x.png", "--model_path", "m.pt"])
+    assert (a["K"], a["sample"], a["baseline_path"], a["n_eval"], a["seed"], a["dim"], a["save"], a["model_path"]) == (
+        12, True, "b.pt", 8, 4, 4, "x.png", "m.pt")
+    for f in (tool.run_online_eval, tool.plot_results, tool.main, tool.random_walk):
+        assert callable(f)
