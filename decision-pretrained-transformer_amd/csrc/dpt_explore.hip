@@ -11,23 +11,21 @@
 // tree): repeated calls are bit-identical.  The weights are exp() of a difference of doubles.
 #include <cmath>
 
-#include "dpt_common.h"
+#include "dpt_chain.h"
 
 namespace dpt {
-
-constexpr int kExThreads = 256;
 
 // ----------------------------------------------------------------------------- every-position cross-entropy
 // One thread per row (b, t) of preds.  The target is tseq[b] or trow[row]; w = weights[row] or 1.
 // rowloss[row] = lse(x) - x[target] (unweighted) and dpreds = scale w (softmax(x) - onehot(target)),
 // stored as exact zeros when w == 0.  A target outside [0, A) reads nothing: zero loss, zero gradient.
-__global__ __launch_bounds__(kExThreads) void ex_ce_rows_kernel(const float* __restrict__ preds,
+__global__ __launch_bounds__(kChainThreads) void ex_ce_rows_kernel(const float* __restrict__ preds,
                                                                 const int64_t* __restrict__ tseq,
                                                                 const int32_t* __restrict__ trow,
                                                                 const double* __restrict__ weights, int B, int T,
                                                                 int A, double scale, double* __restrict__ rowloss,
                                                                 float* __restrict__ dpreds) {
-    const int64_t row = (int64_t)blockIdx.x * kExThreads + threadIdx.x;
+    const int64_t row = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
     if (row >= (int64_t)B * T) return;
     const int64_t tg = tseq ? tseq[row / T] : (int64_t)trow[row];
     float* dx = dpreds ? dpreds + row * A : nullptr;
@@ -49,11 +47,11 @@ __global__ __launch_bounds__(kExThreads) void ex_ce_rows_kernel(const float* __r
 // One thread per (b, j): w = exp((rowloss[b][j+1] - rowloss[b][j]) inv_beta), 0 at j = T - 1.  With
 // `actions` (B, T - 1) the explorer's per-row targets are written alongside: trow[b][j] = actions[b][j],
 // -1 (no class) at j = T - 1.
-__global__ __launch_bounds__(kExThreads) void ex_weights_kernel(const double* __restrict__ rowloss, int B, int T,
+__global__ __launch_bounds__(kChainThreads) void ex_weights_kernel(const double* __restrict__ rowloss, int B, int T,
                                                                 double inv_beta, double* __restrict__ weights,
                                                                 const int32_t* __restrict__ actions,
                                                                 int32_t* __restrict__ trow) {
-    const int64_t row = (int64_t)blockIdx.x * kExThreads + threadIdx.x;
+    const int64_t row = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
     if (row >= (int64_t)B * T) return;
     const int j = (int)(row % T);
     const int64_t b = row / T;
@@ -97,10 +95,9 @@ static int ex_check_shape(const dpt_train_desc* d, int32_t N, int32_t K, dpt_tra
 static int ex_weights(const double* rowloss, int32_t B, int32_t T, double inv_beta, double* weights,
                       const int32_t* actions, int32_t* trow, void* stream) {
     const int64_t rows = (int64_t)B * T;
-    const int64_t blocks = (rows + kExThreads - 1) / kExThreads;
-    DPT_REQUIRE(blocks < (1ll << 31), "explore weights: %lld rows", (long long)rows);
-    hipLaunchKernelGGL(ex_weights_kernel, dim3((unsigned)blocks), dim3(kExThreads), 0, as_stream(stream), rowloss, B,
-                       T, inv_beta, weights, actions, trow);
+    DPT_REQUIRE(chain_blocks(rows) < (1ll << 31), "explore weights: %lld rows", (long long)rows);
+    hipLaunchKernelGGL(ex_weights_kernel, chain_grid(rows), dim3(kChainThreads), 0, as_stream(stream), rowloss, B, T,
+                       inv_beta, weights, actions, trow);
     return launched("ex_weights");
 }
 
@@ -119,10 +116,9 @@ int dpt_train_ce_rows(const float* preds, const int64_t* targets_seq, const int3
     DPT_REQUIRE(batch >= 1 && window >= 1 && A >= 1, "train ce rows: batch=%d window=%d A=%d", batch, window, A);
     if (int rc = check_action_dim("train ce rows", A)) return rc;
     const int64_t rows = (int64_t)batch * window;
-    const int64_t blocks = (rows + kExThreads - 1) / kExThreads;
-    DPT_REQUIRE(blocks < (1ll << 31), "train ce rows: %lld rows", (long long)rows);
-    hipLaunchKernelGGL(ex_ce_rows_kernel, dim3((unsigned)blocks), dim3(kExThreads), 0, as_stream(stream), preds,
-                       targets_seq, targets_row, weights, batch, window, A, scale, rowloss, dpreds);
+    DPT_REQUIRE(chain_blocks(rows) < (1ll << 31), "train ce rows: %lld rows", (long long)rows);
+    hipLaunchKernelGGL(ex_ce_rows_kernel, chain_grid(rows), dim3(kChainThreads), 0, as_stream(stream), preds, targets_seq,
+                       targets_row, weights, batch, window, A, scale, rowloss, dpreds);
     ce_finish(rowloss, weights, rows, scale, loss_acc, as_stream(stream));
     return launched("ex_ce_rows");
 }
@@ -161,53 +157,42 @@ int dpt_explore_grad(const dpt_train_desc* d, const float* explorer_blob, const 
     DPT_REQUIRE(std::isfinite(a->beta) && a->beta > 0.0, "explore grad: beta=%g must be finite and > 0", a->beta);
     const int base = a->type & ~DPT_BANDIT_F32;
     DPT_REQUIRE(base == DPT_BANDIT_GAUSSIAN || base == DPT_BANDIT_BERNOULLI, "explore grad: bandit type %d", a->type);
-    DPT_REQUIRE((a->flags & ~DPT_EXPLORE_ACCUMULATE) == 0, "explore grad: unknown flags 0x%x", a->flags);
+    if (int rc = chain_check_call("explore grad", a->flags, DPT_EXPLORE_ACCUMULATE, a->workspace)) return rc;
     const bool accumulate = (a->flags & DPT_EXPLORE_ACCUMULATE) != 0;
-    DPT_REQUIRE((reinterpret_cast<uintptr_t>(a->workspace) & 15) == 0, "explore grad: workspace not 16-byte aligned");
     ExWs w;
     int64_t nblob = 0;
     if (int rc = ex_ws(&run, w, &nblob)) return rc;
     const int32_t N = a->N, K = a->K, A = run.action_dim;
     float* ws = a->workspace;
-    float *tokens = ws + w.tokens, *preds = ws + w.preds, *dpreds = ws + w.dpreds;
+    const ChainBufs b{ws + w.tokens, ws + w.train, ws + w.preds, ws + w.dpreds, nblob};
     double* rowloss = reinterpret_cast<double*>(ws + w.rowloss);
     double* weights = reinterpret_cast<double*>(ws + w.weights);
     int32_t* trow = reinterpret_cast<int32_t*>(ws + w.trow);
 
     // the explorer's K - 1 steps: its action into the context, the env stepped by a separate arm
-    dpt_bandit_rollout_args r{};
-    r.N = N; r.H = K - 1; r.A = A; r.type = a->type | DPT_BANDIT_F32; r.sample = 1;
-    r.first_task = a->first_task; r.var = a->var; r.seed = a->seed; r.counter = a->counter;
-    r.means = a->means; r.uniforms = a->uniforms; r.noise = a->noise;
-    r.kvcache = ws + w.rollout;
-    r.actions_out = a->actions_out; r.rewards_out = a->rewards_out;
-    r.arm_value_out = reinterpret_cast<double*>(ws + w.arm_value);
-    r.logits_out = nullptr;
+    const dpt_bandit_rollout_args r =
+        chain_rollout_args(*a, A, ws + w.rollout, reinterpret_cast<double*>(ws + w.arm_value));
     if (int rc = dpt_rollout_bandit_generic_env(&run, explorer_blob, &r, a->env_actions, a->env_actions ? 0 : 1,
                                                 a->env_actions_out, stream))
         return rc;
-    if (int rc = dpt_interactive_pack(a->actions_out, a->rewards_out, N, K - 1, A, tokens, stream)) return rc;
+    if (int rc = dpt_interactive_pack(a->actions_out, a->rewards_out, N, K - 1, A, b.tokens, stream)) return rc;
 
+    // each fit's gradient: its dblob itself, or workspace when it is added to the dblob
+    auto fit = [&](const float* blob, float* dblob, auto loss) {
+        return chain_fit(&run, blob, b, accumulate ? ws + w.grad : dblob, accumulate ? dblob : nullptr, loss, stream);
+    };
     // the exploiter: row t of this one forward is its step-t last-position logits
-    float* grad = accumulate ? ws + w.grad : a->dblob_exploiter;
-    if (int rc = dpt_train_forward(&run, exploiter_blob, tokens, ws + w.train, preds, stream)) return rc;
-    if (int rc = dpt_train_ce_rows(preds, a->targets, nullptr, nullptr, N, K, A, a->scale_exploiter, rowloss, dpreds,
-                                   a->loss_exploiter, stream))
+    if (int rc = fit(exploiter_blob, a->dblob_exploiter, [&] {
+            return dpt_train_ce_rows(b.preds, a->targets, nullptr, nullptr, N, K, A, a->scale_exploiter, rowloss,
+                                     b.dpreds, a->loss_exploiter, stream);
+        }))
         return rc;
-    if (int rc = dpt_train_backward(&run, exploiter_blob, tokens, ws + w.train, dpreds, grad, stream)) return rc;
-    if (accumulate)
-        if (int rc = ia_accumulate(a->dblob_exploiter, grad, nblob, stream)) return rc;
-
     // the explorer: weights from the exploiter's row losses, targets = the recorded context actions
     if (int rc = ex_weights(rowloss, N, K, 1.0 / a->beta, weights, a->actions_out, trow, stream)) return rc;
-    grad = accumulate ? ws + w.grad : a->dblob_explorer;
-    if (int rc = dpt_train_forward(&run, explorer_blob, tokens, ws + w.train, preds, stream)) return rc;
-    if (int rc = dpt_train_ce_rows(preds, nullptr, trow, weights, N, K, A, a->scale_explorer, rowloss, dpreds,
-                                   a->loss_explorer, stream))
-        return rc;
-    if (int rc = dpt_train_backward(&run, explorer_blob, tokens, ws + w.train, dpreds, grad, stream)) return rc;
-    if (accumulate) return ia_accumulate(a->dblob_explorer, grad, nblob, stream);
-    return DPT_OK;
+    return fit(explorer_blob, a->dblob_explorer, [&] {
+        return dpt_train_ce_rows(b.preds, nullptr, trow, weights, N, K, A, a->scale_explorer, rowloss, b.dpreds,
+                                 a->loss_explorer, stream);
+    });
 }
 
 }  // extern "C"

@@ -9,21 +9,19 @@
 // once on the store, as ts_ce_kernel (dpt_trainstep.hip) does; the loss is summed in a fixed order
 // (the sequences thread-strided in index order, then an LDS tree): repeated calls are bit-identical.
 // The pack kernel copies and converts each reward to fp32 once: bit-exact.
-#include "dpt_common.h"
+#include "dpt_chain.h"
 
 namespace dpt {
-
-constexpr int kIaThreads = 256;
 
 // ----------------------------------------------------------------------------- pack
 // One thread per output float.  tokens (N, Hc + 1, A + 3): row 0 = [1, 0_A, 0, 0] (the query state
 // of a bandit is 1), row 1 + j = [1, onehot(a_j), 1, float(r_j)] (models/net.py:42-54 with state 1).
 // An action outside [0, A) packs an all-zero one-hot.
-__global__ __launch_bounds__(kIaThreads) void ia_pack_kernel(const int32_t* __restrict__ actions,
+__global__ __launch_bounds__(kChainThreads) void ia_pack_kernel(const int32_t* __restrict__ actions,
                                                              const double* __restrict__ rewards, int N, int Hc,
                                                              int A, float* __restrict__ tokens) {
     const int F = A + 3, T = Hc + 1;
-    const int64_t e = (int64_t)blockIdx.x * kIaThreads + threadIdx.x;
+    const int64_t e = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
     if (e >= (int64_t)N * T * F) return;
     const int f = (int)(e % F);
     const int64_t row = e / F;
@@ -43,11 +41,11 @@ __global__ __launch_bounds__(kIaThreads) void ia_pack_kernel(const int32_t* __re
 // One thread per row (b, t) of preds.  t < T - 1: the row of dpreds is zero.  t = T - 1:
 // partial[b] = lse(x) - x[target_b] and dpreds = scale (softmax(x) - onehot(target_b)).  A target
 // outside [0, A) reads nothing: zero loss, zero gradient.
-__global__ __launch_bounds__(kIaThreads) void ia_ce_last_kernel(const float* __restrict__ preds,
+__global__ __launch_bounds__(kChainThreads) void ia_ce_last_kernel(const float* __restrict__ preds,
                                                                 const int64_t* __restrict__ targets, int B, int T,
                                                                 int A, double scale, float* __restrict__ dpreds,
                                                                 double* __restrict__ partial) {
-    const int64_t row = (int64_t)blockIdx.x * kIaThreads + threadIdx.x;
+    const int64_t row = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
     if (row >= (int64_t)B * T) return;
     const int t = (int)(row % T);
     const int64_t b = row / T;
@@ -68,9 +66,9 @@ __global__ __launch_bounds__(kIaThreads) void ia_ce_last_kernel(const float* __r
 }
 
 // dst += src, element by element (each element has one writer: the order is fixed)
-__global__ __launch_bounds__(kIaThreads) void ia_accumulate_kernel(float* __restrict__ dst,
+__global__ __launch_bounds__(kChainThreads) void ia_accumulate_kernel(float* __restrict__ dst,
                                                                    const float* __restrict__ src, int64_t numel) {
-    const int64_t i = (int64_t)blockIdx.x * kIaThreads + threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * kChainThreads + threadIdx.x;
     if (i < numel) dst[i] += src[i];
 }
 
@@ -100,30 +98,18 @@ static int ia_ws(const dpt_train_desc* run, IaWs& w, int64_t* nblob_out) {
     return DPT_OK;
 }
 
-// the shape checks shared by the workspace queries and the steps of the interactive (`who` =
-// "interactive", min_K 1) and the explorer/exploiter (dpt_explore.hip) training steps; fills `run`
+// the bandit chains' shape checks (dpt_chain.h); also the explorer/exploiter step's (dpt_explore.hip)
 int ia_check_shape(const dpt_train_desc* d, int32_t N, int32_t K, int32_t min_K, const char* who,
                    dpt_train_desc& run) {
-    DPT_REQUIRE(d != nullptr, "%s: null desc", who);
-    DPT_REQUIRE(N >= 1, "%s: N=%d", who, N);
-    DPT_REQUIRE(K >= min_K, "%s: K=%d (at least %d)", who, K, min_K);
-    DPT_REQUIRE(K <= d->n_positions, "%s: K=%d exceeds n_positions=%d", who, K, d->n_positions);
-    DPT_REQUIRE((int64_t)N * K <= (1ll << 26), "%s: N * K = %lld rows (use smaller chunks)", who, (long long)N * K);
-    DPT_REQUIRE(d->state_dim == 1, "%s: state_dim=%d (bandits have state_dim 1)", who, d->state_dim);
-    if (int rc = check_action_dim(who, d->action_dim)) return rc;
-    DPT_REQUIRE(d->dropout == 0.0f, "%s: dropout=%g must be 0 (the cached decode has no dropout masks)", who,
-                (double)d->dropout);
-    run = *d;
-    run.batch = N;
-    run.window = K;
-    run.reserved = 0;
-    return DPT_OK;
+    auto bandit = [who](const dpt_train_desc* d) -> int {
+        DPT_REQUIRE(d->state_dim == 1, "%s: state_dim=%d (bandits have state_dim 1)", who, d->state_dim);
+        return check_action_dim(who, d->action_dim);
+    };
+    return chain_check_shape(d, N, K, min_K, who, "the cached decode has no dropout masks", bandit, run);
 }
 
-// dst += src over `numel` floats, one launch on `stream`
 int ia_accumulate(float* dst, const float* src, int64_t numel, void* stream) {
-    const int64_t blocks = (numel + kIaThreads - 1) / kIaThreads;
-    hipLaunchKernelGGL(ia_accumulate_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, as_stream(stream), dst, src,
+    hipLaunchKernelGGL(ia_accumulate_kernel, chain_grid(numel), dim3(kChainThreads), 0, as_stream(stream), dst, src,
                        numel);
     return launched("ia_accumulate");
 }
@@ -139,10 +125,9 @@ int dpt_interactive_pack(const int32_t* actions, const double* rewards, int32_t 
     DPT_REQUIRE(tokens && (Hc == 0 || (actions && rewards)), "interactive pack: null pointer");
     DPT_REQUIRE(N >= 1 && Hc >= 0 && A >= 1, "interactive pack: N=%d Hc=%d A=%d", N, Hc, A);
     const int64_t total = (int64_t)N * (Hc + 1ll) * (A + 3);
-    const int64_t blocks = (total + kIaThreads - 1) / kIaThreads;
-    DPT_REQUIRE(blocks < (1ll << 31), "interactive pack: %lld elements", (long long)total);
-    hipLaunchKernelGGL(ia_pack_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, as_stream(stream), actions,
-                       rewards, N, Hc, A, tokens);
+    DPT_REQUIRE(chain_blocks(total) < (1ll << 31), "interactive pack: %lld elements", (long long)total);
+    hipLaunchKernelGGL(ia_pack_kernel, chain_grid(total), dim3(kChainThreads), 0, as_stream(stream), actions, rewards,
+                       N, Hc, A, tokens);
     return launched("ia_pack");
 }
 
@@ -152,10 +137,9 @@ int dpt_train_ce_last(const float* preds, const int64_t* targets, int32_t batch,
     DPT_REQUIRE(batch >= 1 && window >= 1 && A >= 1, "train ce last: batch=%d window=%d A=%d", batch, window, A);
     if (int rc = check_action_dim("train ce last", A)) return rc;
     const int64_t rows = (int64_t)batch * window;
-    const int64_t blocks = (rows + kIaThreads - 1) / kIaThreads;
-    DPT_REQUIRE(blocks < (1ll << 31), "train ce last: %lld rows", (long long)rows);
-    hipLaunchKernelGGL(ia_ce_last_kernel, dim3((unsigned)blocks), dim3(kIaThreads), 0, as_stream(stream), preds,
-                       targets, batch, window, A, scale, dpreds, partial);
+    DPT_REQUIRE(chain_blocks(rows) < (1ll << 31), "train ce last: %lld rows", (long long)rows);
+    hipLaunchKernelGGL(ia_ce_last_kernel, chain_grid(rows), dim3(kChainThreads), 0, as_stream(stream), preds, targets,
+                       batch, window, A, scale, dpreds, partial);
     ce_finish(partial, nullptr, batch, scale, loss_acc, as_stream(stream));
     return launched("ia_ce_last");
 }
@@ -179,39 +163,30 @@ int dpt_interactive_grad(const dpt_train_desc* d, const float* blob, const dpt_i
     const int base = a->type & ~DPT_BANDIT_F32;
     DPT_REQUIRE(base == DPT_BANDIT_GAUSSIAN || base == DPT_BANDIT_BERNOULLI, "interactive grad: bandit type %d",
                 a->type);
-    DPT_REQUIRE((a->flags & ~(DPT_INTERACTIVE_ACCUMULATE | DPT_INTERACTIVE_FULL_WIDTH)) == 0,
-                "interactive grad: unknown flags 0x%x", a->flags);
+    if (int rc = chain_check_call("interactive grad", a->flags, DPT_INTERACTIVE_ACCUMULATE | DPT_INTERACTIVE_FULL_WIDTH,
+                                  a->workspace))
+        return rc;
     const bool accumulate = (a->flags & DPT_INTERACTIVE_ACCUMULATE) != 0;
-    DPT_REQUIRE((reinterpret_cast<uintptr_t>(a->workspace) & 15) == 0,
-                "interactive grad: workspace not 16-byte aligned");
     IaWs w;
     int64_t nblob = 0;
     if (int rc = ia_ws(&run, w, &nblob)) return rc;
     const int32_t N = a->N, K = a->K, A = run.action_dim;
     float* ws = a->workspace;
-    float *tokens = ws + w.tokens, *preds = ws + w.preds, *dpreds = ws + w.dpreds;
-    float* grad = accumulate ? ws + w.grad : a->dblob;
+    const ChainBufs b{ws + w.tokens, ws + w.train, ws + w.preds, ws + w.dpreds, nblob};
     dpt_train_desc fit = run;  // the training forward / backward: the loss reads the last position only
     if (!(a->flags & DPT_INTERACTIVE_FULL_WIDTH)) fit.reserved = DPT_TRAIN_LAST_LOSS;
     double* partial = reinterpret_cast<double*>(ws + w.partial);
     if (K > 1) {
-        dpt_bandit_rollout_args r{};
-        r.N = N; r.H = K - 1; r.A = A; r.type = a->type | DPT_BANDIT_F32; r.sample = 1;
-        r.first_task = a->first_task; r.var = a->var; r.seed = a->seed; r.counter = a->counter;
-        r.means = a->means; r.uniforms = a->uniforms; r.noise = a->noise;
-        r.kvcache = ws + w.rollout;
-        r.actions_out = a->actions_out; r.rewards_out = a->rewards_out;
-        r.arm_value_out = reinterpret_cast<double*>(ws + w.arm_value);
-        r.logits_out = nullptr;
+        const dpt_bandit_rollout_args r =
+            chain_rollout_args(*a, A, ws + w.rollout, reinterpret_cast<double*>(ws + w.arm_value));
         if (int rc = dpt_rollout_bandit_generic(&run, blob, &r, stream)) return rc;
     }
-    if (int rc = dpt_interactive_pack(a->actions_out, a->rewards_out, N, K - 1, A, tokens, stream)) return rc;
-    if (int rc = dpt_train_forward(&fit, blob, tokens, ws + w.train, preds, stream)) return rc;
-    if (int rc = dpt_train_ce_last(preds, a->targets, N, K, A, a->scale, dpreds, partial, a->loss_acc, stream))
-        return rc;
-    if (int rc = dpt_train_backward(&fit, blob, tokens, ws + w.train, dpreds, grad, stream)) return rc;
-    if (accumulate) return ia_accumulate(a->dblob, grad, nblob, stream);
-    return DPT_OK;
+    if (int rc = dpt_interactive_pack(a->actions_out, a->rewards_out, N, K - 1, A, b.tokens, stream)) return rc;
+    auto loss = [&] {
+        return dpt_train_ce_last(b.preds, a->targets, N, K, A, a->scale, b.dpreds, partial, a->loss_acc, stream);
+    };
+    // the chunk's gradient: dblob itself, or workspace when it is added to dblob
+    return chain_fit(&fit, blob, b, accumulate ? ws + w.grad : a->dblob, accumulate ? a->dblob : nullptr, loss, stream);
 }
 
 }  // extern "C"

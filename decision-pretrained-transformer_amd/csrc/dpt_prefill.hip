@@ -53,6 +53,74 @@ __device__ inline float token_feature(const PrefillArgs& a, int sd, int A, int n
     return a.rewards[j];
 }
 
+// ----------------------------------------------------------------------------- the shared window forward
+// The pieces prefill_kernel and rollout_darkroom_episode_kernel are both made of.  Force-inlined: each
+// kernel is compiled as if it held them itself.  A compile-time feature / action count (kF, kA > 0; the
+// episode kernel's) unrolls the loop over it; 0 leaves the loop over the model's runtime count as it is.
+
+// the model-level parameters into LDS (PfTop); the caller's barrier follows.  (nthreads unsigned, as
+// blockDim.x is: with a signed stride the compiler unrolls these loops, 600 instructions a kernel.)
+__device__ __forceinline__ void load_top_params(float* P, const PfTop& pt, const ModelView& M, int F, int A, int tid,
+                                                unsigned nthreads) {
+    for (int i = tid; i < kE; i += nthreads) {
+        P[pt.lnf_g + i] = M.lnf_g[i];
+        P[pt.lnf_b + i] = M.lnf_b[i];
+        P[pt.emb_b + i] = M.emb_b[i];
+    }
+    for (int i = tid; i < kE * A; i += nthreads) P[pt.head_w + (i % A) * kE + i / A] = M.head_w[i];
+    for (int i = tid; i < A; i += nthreads) P[pt.head_b + i] = M.head_b[i];
+    for (int i = tid; i < F * kE; i += nthreads) P[pt.emb_w + i] = M.emb_w[i];
+}
+
+// embed_transition of one token for the lane's 8 columns: the bias, then the F features in order
+// (feat(f) = feature f of the token)
+template <int kF, class Feat>
+__device__ __forceinline__ void embed_acc(const float* P, const PfTop& pt, int g, int F, Feat feat, floatx4& acc0,
+                                          floatx4& acc1) {
+    acc0 = ld4(P + pt.emb_b + 4 * g), acc1 = ld4(P + pt.emb_b + 16 + 4 * g);
+    auto one = [&](int f) {
+        const float v = feat(f);
+        const floatx4 w0 = ld4(P + pt.emb_w + f * kE + 4 * g), w1 = ld4(P + pt.emb_w + f * kE + 16 + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            acc0[r] = fmaf(v, w0[r], acc0[r]);
+            acc1[r] = fmaf(v, w1[r], acc1[r]);
+        }
+    };
+    if constexpr (kF > 0) {
+#pragma unroll
+        for (int f = 0; f < kF; ++f) one(f);
+    } else {
+        for (int f = 0; f < F; ++f) one(f);
+    }
+}
+
+// ln_f + pred_actions of one 16-token block: emit(act, logit) per action, the logit of the lane's token
+// (column lane & 15) on every lane.  ln_f / head over every column keeps the permlane reductions uniform.
+template <int kA, class Emit>
+__device__ __forceinline__ void head_block(const float* P, const PfTop& pt, const float (&xj)[8], int A, Emit emit) {
+    const int g = lane_id() >> 4;
+    float xf[8];
+    ln_cols(xj, xf, P + pt.lnf_g, P + pt.lnf_b);
+    auto one = [&](int act) {
+        const floatx4 w0 = ld4(P + pt.head_w + act * kE + 4 * g);
+        const floatx4 w1 = ld4(P + pt.head_w + act * kE + 16 + 4 * g);
+        float part = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            part = fmaf(xf[r], w0[r], part);
+            part = fmaf(xf[4 + r], w1[r], part);
+        }
+        emit(act, sum_cols(part) + P[pt.head_b + act]);
+    };
+    if constexpr (kA > 0) {
+#pragma unroll
+        for (int act = 0; act < kA; ++act) one(act);
+    } else {
+        for (int act = 0; act < A; ++act) one(act);
+    }
+}
+
 template <int NW>
 __global__ void __launch_bounds__(NW * 64, (NW + 3) / 4)
 prefill_kernel(ModelView M, PrefillArgs a) {
@@ -67,14 +135,7 @@ prefill_kernel(ModelView M, PrefillArgs a) {
     const PfTop pt = PfTop::make(L, F, A);
     const FragSrc3 split0{__builtin_amdgcn_make_buffer_rsrc((void*)a.frag, (short)0, L * Frag3::bytes, 0x00020000), 0};
     load_layer_params(P, M, tid, blockDim.x);
-    for (int i = tid; i < kE; i += blockDim.x) {
-        P[pt.lnf_g + i] = M.lnf_g[i];
-        P[pt.lnf_b + i] = M.lnf_b[i];
-        P[pt.emb_b + i] = M.emb_b[i];
-    }
-    for (int i = tid; i < kE * A; i += blockDim.x) P[pt.head_w + (i % A) * kE + i / A] = M.head_w[i];
-    for (int i = tid; i < A; i += blockDim.x) P[pt.head_b + i] = M.head_b[i];
-    for (int i = tid; i < F * kE; i += blockDim.x) P[pt.emb_w + i] = M.emb_w[i];
+    load_top_params(P, pt, M, F, A, tid, blockDim.x);
     __syncthreads();
 
     const int nqb = (T + 15) >> 4;
@@ -91,16 +152,8 @@ prefill_kernel(ModelView M, PrefillArgs a) {
             for (int k = 0; k < 8; ++k) x[j][k] = 0.f;
             const int tok = qb[j] * 16 + (lane & 15);
             if (j >= nb || tok >= T) continue;
-            floatx4 acc0 = ld4(P + pt.emb_b + 4 * g), acc1 = ld4(P + pt.emb_b + 16 + 4 * g);
-            for (int f = 0; f < F; ++f) {
-                const float v = token_feature(a, sd, A, n, tok, f);
-                const floatx4 w0 = ld4(P + pt.emb_w + f * kE + 4 * g), w1 = ld4(P + pt.emb_w + f * kE + 16 + 4 * g);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    acc0[r] = fmaf(v, w0[r], acc0[r]);
-                    acc1[r] = fmaf(v, w1[r], acc1[r]);
-                }
-            }
+            floatx4 acc0, acc1;
+            embed_acc<0>(P, pt, g, F, [&](int f) { return token_feature(a, sd, A, n, tok, f); }, acc0, acc1);
             const floatx4 p0 = ld4(M.wpe + (size_t)tok * kE + 4 * g), p1 = ld4(M.wpe + (size_t)tok * kE + 16 + 4 * g);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -110,6 +163,8 @@ prefill_kernel(ModelView M, PrefillArgs a) {
         }
     }
 
+    // (the layer loop is not one of the shared pieces: as a force-inlined function it compiles to other code
+    // in the episode kernel, which then runs a K = 100 episode 1.6 % slower, past the round-to-round spread)
     for (int layer = 0; layer < L; ++layer) {
         const float* W = P + layer * PL::size;
         const FragSrc3 fs = split0.layer(layer);
@@ -145,24 +200,12 @@ prefill_kernel(ModelView M, PrefillArgs a) {
             if (j >= nb) break;
             const int tok = qb[j] * 16 + c;
             const bool want = a.out_mode == 0 ? tok == T - 1 : (tok >= 1 && tok < T);
-            // ln_f / head over every column keeps the permlane reductions uniform
-            float xf[8];
-            ln_cols(x[j], xf, P + pt.lnf_g, P + pt.lnf_b);
-            for (int act = 0; act < A; ++act) {
-                const floatx4 w0 = ld4(P + pt.head_w + act * kE + 4 * g);
-                const floatx4 w1 = ld4(P + pt.head_w + act * kE + 16 + 4 * g);
-                float part = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    part = fmaf(xf[r], w0[r], part);
-                    part = fmaf(xf[4 + r], w1[r], part);
-                }
-                const float lg = sum_cols(part) + P[pt.head_b + act];
+            head_block<0>(P, pt, x[j], A, [&](int act, float lg) {
                 if (want && g == 0) {
                     if (a.out_mode == 0) a.out[(size_t)n * A + act] = lg;
                     else a.out[((size_t)n * a.C + (tok - 1)) * A + act] = lg;
                 }
-            }
+            });
         }
     }
 }
@@ -175,6 +218,8 @@ constexpr int kPrefillMaxT = 512;
 constexpr size_t prefill_kv_bytes(int t) {
     return t == 128 ? sizeof(KVBuf<128>) : t == 256 ? sizeof(KVBuf<256>) : sizeof(KVBuf<512>);
 }
+// the geometry (its window: 128, 256 or 512 tokens) that runs a window of T tokens
+constexpr int prefill_geometry(int T) { return T <= 128 ? 128 : T <= 256 ? 256 : 512; }
 
 // Whether a `dyn`-byte parameter block fits in LDS next to that K/V buffer: the one
 // test behind both prefill_max_window (what dpt_forward_window routes by) and the
@@ -190,38 +235,15 @@ int prefill_max_window(const ModelView& M) {
     return 0;
 }
 
-template <int NW>
-static int launch_nw(const ModelView& M, const PrefillArgs& a, size_t dyn, hipStream_t st) {
-    if (!prefill_fits(dyn, 32 * NW)) {
-        set_error(DPT_EUNSUPPORTED, "prefill: parameter block does not fit in LDS");
-        return DPT_EUNSUPPORTED;
-    }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(prefill_kernel<NW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    hipLaunchKernelGGL(prefill_kernel<NW>, dim3(a.N), dim3(NW * 64), dyn, st, M, a);
-    return check_hip(hipGetLastError(), "prefill_kernel launch");
-}
-
-int launch_prefill(const ModelView& M, const float* frag, const float* q, const float* cs, const float* ca,
-                   const float* cn, const float* cr, int N, int C, int out_mode, float* out, hipStream_t st) {
-    PrefillArgs a{q, cs, ca, cn, cr, N, C, out_mode, out, frag};
-    const size_t dyn = sizeof(float) * (size_t)PfTop::make(M.n_layer, M.F, M.A).total;
-    const int T = C + 1;
-    if (T <= 128) return launch_nw<4>(M, a, dyn, st);
-    if (T <= 256) return launch_nw<8>(M, a, dyn, st);
-    return launch_nw<16>(M, a, dyn, st);
-}
-
 // ----------------------------------------------------------------------------- the episode rollout
 // The in-episode DarkRoom rollout (include/dpt_hip.h, dpt_rollout_darkroom_episode) in one launch: one
 // workgroup per env runs the K steps of the episode.  Step t embeds the window W_t (T = t + 1 tokens:
 // the query state s_t at position 0, then the episode's own t transitions) from the records the
-// workgroup keeps in LDS, runs prefill_kernel's forward over it (the same helpers in the same order, the
-// block count growing with t), reads the logits of position T - 1, and one thread selects, moves and
-// appends to the records.  The model's parameter block is loaded once per launch, not per step; the
-// records reach global memory once, after the last step.
+// workgroup keeps in LDS, runs the shared window forward over it (prefill_kernel's, the block count
+// growing with t), reads the logits of position T - 1, and one thread selects, moves and appends to the
+// records (darkroom_act, dpt_darkroom_env.h).  The model's parameter block is loaded once per launch,
+// not per step; the records reach global memory once, after the last step.
 
-constexpr int kEpA = 5, kEpF = 10;  // DarkRoom: 5 actions, tokens [s (2) | onehot(a) (5) | s' (2) | r]
 constexpr int kEpGx = 0, kEpGy = 1, kEpRet = 2;  // EpLds::perm's tail
 
 struct EpisodeArgs {
@@ -269,29 +291,22 @@ rollout_darkroom_episode_kernel(ModelView M, EpisodeArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = M.n_layer, K = a.K;
     const float scale = 0.17677669529663687f;  // 1/sqrt(head_dim = 32)
-    const PfTop pt = PfTop::make(L, kEpF, kEpA);
+    const PfTop pt = PfTop::make(L, kDarkroomF, kDarkroomA);
     const EpLds el = EpLds::make(K);
     unsigned char* R = reinterpret_cast<unsigned char*>(P + pt.total);
     double* u_ep = reinterpret_cast<double*>(R + el.u);
     float* lg_s = reinterpret_cast<float*>(R + el.lg);
     int32_t* perm_s = reinterpret_cast<int32_t*>(R + el.perm);
-    int32_t* env_s = perm_s + kEpA;  // goal x, goal y, the return so far
+    int32_t* env_s = perm_s + kDarkroomA;  // goal x, goal y, the return so far
     int32_t** out_s = reinterpret_cast<int32_t**>(R + el.out);
     unsigned char *st = R + el.st, *ac = R + el.act, *rw = R + el.rew, *tg = R + el.tgt;
     const FragSrc3 split0{__builtin_amdgcn_make_buffer_rsrc((void*)a.frag, (short)0, L * Frag3::bytes, 0x00020000), 0};
     load_layer_params(P, M, tid, blockDim.x);
-    for (int i = tid; i < kE; i += blockDim.x) {
-        P[pt.lnf_g + i] = M.lnf_g[i];
-        P[pt.lnf_b + i] = M.lnf_b[i];
-        P[pt.emb_b + i] = M.emb_b[i];
-    }
-    for (int i = tid; i < kE * kEpA; i += blockDim.x) P[pt.head_w + (i % kEpA) * kE + i / kEpA] = M.head_w[i];
-    for (int i = tid; i < kEpA; i += blockDim.x) P[pt.head_b + i] = M.head_b[i];
-    for (int i = tid; i < kEpF * kE; i += blockDim.x) P[pt.emb_w + i] = M.emb_w[i];
+    load_top_params(P, pt, M, kDarkroomF, kDarkroomA, tid, blockDim.x);
     // the env: permutation, goal, s_0 = (0, 0) and its expert action.  What only the selecting thread
     // or the epilogue reads (goal, return, output pointers) waits in LDS, not in registers held across
     // the step loop.
-    if (tid < kEpA) perm_s[tid] = a.perm ? a.perm[(size_t)n * kEpA + tid] : tid;
+    if (tid < kDarkroomA) perm_s[tid] = a.perm ? a.perm[(size_t)n * kDarkroomA + tid] : tid;
     // the episode's selection uniforms up front, one thread per step (off the serial select chain)
     if (a.sample)
         for (int t = tid; t < K - 1; t += blockDim.x)
@@ -302,9 +317,10 @@ rollout_darkroom_episode_kernel(ModelView M, EpisodeArgs a) {
         env_s[kEpGx] = gx;
         env_s[kEpGy] = gy;
         env_s[kEpRet] = 0;
-        st[0] = 0;
-        st[1] = 0;
-        tg[0] = (unsigned char)darkroom_opt(0, 0, gx, gy, a.perm ? a.perm + (size_t)n * kEpA : nullptr);
+        int x0, y0;
+        tg[0] = (unsigned char)darkroom_reset(x0, y0, gx, gy, a.perm ? a.perm + (size_t)n * kDarkroomA : nullptr);
+        st[0] = (unsigned char)x0;
+        st[1] = (unsigned char)y0;
         out_s[0] = a.states + (size_t)n * 2 * K;
         out_s[1] = a.actions + (size_t)n * (K - 1);
         out_s[2] = a.rewards + (size_t)n * (K - 1);
@@ -342,29 +358,21 @@ rollout_darkroom_episode_kernel(ModelView M, EpisodeArgs a) {
                 const int tok = qb[j] * 16 + (lane & 15);
                 if (j >= nb || tok >= T) continue;
                 const int sj = tok == 0 ? T - 1 : tok - 1;
-                float v[kEpF];
+                float v[kDarkroomF];
 #pragma unroll
-                for (int f = 0; f < kEpF; ++f) v[f] = zero;
+                for (int f = 0; f < kDarkroomF; ++f) v[f] = zero;
                 v[0] = (float)st[2 * sj];
                 v[1] = (float)st[2 * sj + 1];
                 if (tok > 0) {
                     const int aj = ac[sj];
 #pragma unroll
-                    for (int k = 0; k < kEpA; ++k) v[2 + k] = aj == k ? 1.f : zero;
-                    v[2 + kEpA] = (float)st[2 * tok];
-                    v[3 + kEpA] = (float)st[2 * tok + 1];
-                    v[4 + kEpA] = (float)rw[sj];
+                    for (int k = 0; k < kDarkroomA; ++k) v[2 + k] = aj == k ? 1.f : zero;
+                    v[2 + kDarkroomA] = (float)st[2 * tok];
+                    v[3 + kDarkroomA] = (float)st[2 * tok + 1];
+                    v[4 + kDarkroomA] = (float)rw[sj];
                 }
-                floatx4 acc0 = ld4(P + pt.emb_b + 4 * g), acc1 = ld4(P + pt.emb_b + 16 + 4 * g);
-#pragma unroll
-                for (int f = 0; f < kEpF; ++f) {
-                    const floatx4 w0 = ld4(P + pt.emb_w + f * kE + 4 * g), w1 = ld4(P + pt.emb_w + f * kE + 16 + 4 * g);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        acc0[r] = fmaf(v[f], w0[r], acc0[r]);
-                        acc1[r] = fmaf(v[f], w1[r], acc1[r]);
-                    }
-                }
+                floatx4 acc0, acc1;
+                embed_acc<kDarkroomF>(P, pt, g, kDarkroomF, [&](int f) { return v[f]; }, acc0, acc1);
                 // (buffer loads at a 32-bit byte offset: a 64-bit per-lane address takes a zero half, a
                 // constant register that is hoisted out of the step loop and spilled across the layers)
                 const int po = (tok * kE + 4 * g) * 4;
@@ -418,50 +426,35 @@ rollout_darkroom_episode_kernel(ModelView M, EpisodeArgs a) {
             // stores with the zero register of x's initial value, kept (spilled) across the layers
             int z0 = 0;
             asm volatile("" : "+v"(z0));
-            float* lg_out = a.logits ? a.logits + ((size_t)n * K + (T - 1)) * kEpA + z0 : nullptr;
+            float* lg_out = a.logits ? a.logits + ((size_t)n * K + (T - 1)) * kDarkroomA + z0 : nullptr;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 if (j >= nb || qb[j] != qlast) continue;  // wave-uniform
-                float xf[8];
-                ln_cols(x[j], xf, P + pt.lnf_g, P + pt.lnf_b);
-#pragma unroll
-                for (int act = 0; act < kEpA; ++act) {
-                    const floatx4 w0 = ld4(P + pt.head_w + act * kE + 4 * g);
-                    const floatx4 w1 = ld4(P + pt.head_w + act * kE + 16 + 4 * g);
-                    float part = 0.f;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        part = fmaf(xf[r], w0[r], part);
-                        part = fmaf(xf[4 + r], w1[r], part);
-                    }
-                    const float lg = sum_cols(part) + P[pt.head_b + act];
+                head_block<kDarkroomA>(P, pt, x[j], kDarkroomA, [&](int act, float lg) {
                     if (g == 0 && c == clast) {
                         lg_s[act] = lg;
                         if (lg_out) lg_out[act] = lg;
                     }
-                }
+                });
             }
         }
         bar_lds();
-        // one thread: dpt_select_action's rule (mdp_act_kernel's call), the move, the reward and the next
-        // expert action, appended to the records.  The K-th action is never drawn.
+        // one thread: the act rule (darkroom_act, mdp_act_kernel's call) appended to the records.  The K-th
+        // action is never drawn.
         if (tid == 0 && T < K) {
-            float lg[kEpA];
+            float lg[kDarkroomA];
 #pragma unroll
-            for (int k = 0; k < kEpA; ++k) lg[k] = lg_s[k];
+            for (int k = 0; k < kDarkroomA; ++k) lg[k] = lg_s[k];
             const double u = a.sample ? u_ep[T - 1] : 0.0;
-            const int act = select_fixed_fast<kEpA>(lg, a.sample, 1.0f, u);
-            const int32_t* pm = a.perm ? perm_s : nullptr;
             int cur_x = st[2 * (T - 1)], cur_y = st[2 * (T - 1) + 1];
-            const int gx = env_s[kEpGx], gy = env_s[kEpGy];
-            darkroom_move(cur_x, cur_y, pm ? pm[act] : act, a.dim);
-            const int r = (cur_x == gx && cur_y == gy) ? 1 : 0;
-            env_s[kEpRet] += r;
-            ac[T - 1] = (unsigned char)act;
-            rw[T - 1] = (unsigned char)r;
+            const DarkroomStep step = darkroom_act(lg, a.sample, u, a.perm ? perm_s : nullptr, a.dim, env_s[kEpGx],
+                                                   env_s[kEpGy], cur_x, cur_y);
+            env_s[kEpRet] += step.reward;
+            ac[T - 1] = (unsigned char)step.action;
+            rw[T - 1] = (unsigned char)step.reward;
             st[2 * T] = (unsigned char)cur_x;
             st[2 * T + 1] = (unsigned char)cur_y;
-            tg[T] = (unsigned char)darkroom_opt(cur_x, cur_y, gx, gy, pm);
+            tg[T] = (unsigned char)step.next_opt;
         }
         bar_lds();
     }
@@ -477,27 +470,49 @@ rollout_darkroom_episode_kernel(ModelView M, EpisodeArgs a) {
     if (tid == 0 && o_ret) *o_ret = env_s[kEpRet];
 }
 
+// ----------------------------------------------------------------------------- the launches
+// One workgroup of NW waves per sequence / env with `dyn` bytes of dynamic LDS, on the geometry that
+// runs windows of T tokens; the callers have checked prefill_fits(dyn, prefill_geometry(T)).
 template <int NW>
-static int launch_episode_nw(const ModelView& M, const EpisodeArgs& a, size_t dyn, hipStream_t st) {
-    if (!prefill_fits(dyn, 32 * NW)) {
-        set_error(DPT_EUNSUPPORTED, "darkroom episode: parameter block and records (%zu bytes) do not fit in LDS", dyn);
+static auto kernel_of(const PrefillArgs&) { return prefill_kernel<NW>; }
+template <int NW>
+static auto kernel_of(const EpisodeArgs&) { return rollout_darkroom_episode_kernel<NW>; }
+
+template <int NW, class Args>
+static int launch_nw(const char* what, const ModelView& M, const Args& a, size_t dyn, hipStream_t st) {
+    const auto kernel = kernel_of<NW>(a);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)dyn);
+    hipLaunchKernelGGL(kernel, dim3(a.N), dim3(NW * 64), dyn, st, M, a);
+    return check_hip(hipGetLastError(), what);
+}
+template <class Args>
+static int launch_window(const char* what, int T, const ModelView& M, const Args& a, size_t dyn, hipStream_t st) {
+    if (T <= 128) return launch_nw<4>(what, M, a, dyn, st);
+    if (T <= 256) return launch_nw<8>(what, M, a, dyn, st);
+    return launch_nw<16>(what, M, a, dyn, st);
+}
+
+int launch_prefill(const ModelView& M, const float* frag, const float* q, const float* cs, const float* ca,
+                   const float* cn, const float* cr, int N, int C, int out_mode, float* out, hipStream_t st) {
+    PrefillArgs a{q, cs, ca, cn, cr, N, C, out_mode, out, frag};
+    const size_t dyn = sizeof(float) * (size_t)PfTop::make(M.n_layer, M.F, M.A).total;
+    if (!prefill_fits(dyn, prefill_geometry(C + 1))) {
+        set_error(DPT_EUNSUPPORTED, "prefill: parameter block does not fit in LDS");
         return DPT_EUNSUPPORTED;
     }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_darkroom_episode_kernel<NW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    hipLaunchKernelGGL(rollout_darkroom_episode_kernel<NW>, dim3(a.N), dim3(NW * 64), dyn, st, M, a);
-    return check_hip(hipGetLastError(), "rollout_darkroom_episode_kernel launch");
+    return launch_window("prefill_kernel launch", C + 1, M, a, dyn, st);
 }
 
 // Bytes of dynamic LDS of an episode of K steps for a model of n_layer blocks, and whether they fit
 // next to the K/V buffer of the geometry K runs on (a host-only test: dpt_rollout_darkroom_episode's
 // unsupported-shape check, made before any launch).
 static size_t episode_dyn_bytes(int n_layer, int K) {
-    return sizeof(float) * (size_t)PfTop::make(n_layer, kEpF, kEpA).total + (size_t)EpLds::make(K).total;
+    return sizeof(float) * (size_t)PfTop::make(n_layer, kDarkroomF, kDarkroomA).total + (size_t)EpLds::make(K).total;
 }
 bool darkroom_episode_fits(int n_layer, int K) {
     if (K > kPrefillMaxT) return false;
-    return prefill_fits(episode_dyn_bytes(n_layer, K), K <= 128 ? 128 : K <= 256 ? 256 : 512);
+    return prefill_fits(episode_dyn_bytes(n_layer, K), prefill_geometry(K));
 }
 
 int launch_darkroom_episode(const ModelView& M, const float* frag, const dpt_darkroom_episode_args& h,
@@ -505,9 +520,11 @@ int launch_darkroom_episode(const ModelView& M, const float* frag, const dpt_dar
     EpisodeArgs a{h.N,     h.K,      h.dim,     h.sample,  h.first_task, h.seed,   h.counter, h.goal, h.perm,
                   h.uniforms, h.states, h.actions, h.rewards, h.targets,    h.logits, h.returns, frag};
     const size_t dyn = episode_dyn_bytes(M.n_layer, h.K);
-    if (h.K <= 128) return launch_episode_nw<4>(M, a, dyn, st);
-    if (h.K <= 256) return launch_episode_nw<8>(M, a, dyn, st);
-    return launch_episode_nw<16>(M, a, dyn, st);
+    if (!prefill_fits(dyn, prefill_geometry(h.K))) {
+        set_error(DPT_EUNSUPPORTED, "darkroom episode: parameter block and records (%zu bytes) do not fit in LDS", dyn);
+        return DPT_EUNSUPPORTED;
+    }
+    return launch_window("rollout_darkroom_episode_kernel launch", h.K, M, a, dyn, st);
 }
 
 }  // namespace dpt

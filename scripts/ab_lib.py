@@ -8,8 +8,11 @@ layer-0 workspace / the logits memo (suffixes in that order: lib.so+nows+nomemo)
 Env: AB_H, AB_N, AB_A, AB_TILE, AB_ROUNDS.
 AB_WL=train: the training entry points instead (trunk forward / backward, generic rollout, the three
 cross-entropies, the fused steps and the four trainer classes over several steps): one sha1 per case over
-the raw bytes of every output, then the ms per dpt_train_step at the shapes of scripts/train_timing.py
-(AB_STEPS steps between device events) and the host microseconds to enqueue one step of each trainer.
+the raw bytes of every output (group 5: the width-32 window forward, the DarkRoom episode rollout, the
+interactive DarkRoom step and the chains' workspace sizes), then the ms per dpt_train_step at the shapes of
+scripts/train_timing.py (AB_STEPS steps between device events), the host microseconds to enqueue one step of each
+trainer, and the ms per call of the window forward, the episode rollout and the interactive DarkRoom step
+(``window_ms``).  AB_DIGEST_ROUNDS: compute the digests in that many first rounds only.
 The parent exits 1 when two arguments' digests differ and writes digests.txt / ab.json to AB_OUT
 (default profiles/train_refactor); ab.json's ``over_margin`` lists the figures whose median exceeds the
 first argument's by more than the first argument's own max - min."""
@@ -123,7 +126,97 @@ def train_digests():
         out[f"explore E{E}"] = sha(t.explorer_blob, t.exploiter_blob, t.explorer_dblob, t.exploiter_dblob,
                                    t.loss_explorer, t.loss_exploiter, *recs)
         trainer_digests(out, tr, model, E, A, L)
+    window_digests(out, tr)
     return out
+
+
+def window_digests(out, tr):
+    """Group 5: the width-32 window forward (prefill) and what is built on it or beside it -- the one-launch
+    DarkRoom episode rollout, the interactive DarkRoom step and its two kernels called directly, and the three
+    chains' workspace sizes.  Two layers, three sequences / envs, at the smallest windows that reach every
+    geometry (4, 8 and 16 waves) and both parities of the 16-token block count."""
+    import torch
+    import dpt_hip
+    from dpt_hip import _lib, _p, _stream
+    from models.net import Transformer
+    dev, A, L = torch.device("cuda"), 5, 2
+
+    def model(seed, H, sd, E=32):
+        torch.manual_seed(seed)
+        return Transformer(dict(horizon=H, state_dim=sd, action_dim=A, n_layer=L, n_embd=E, n_head=1, dropout=0.0,
+                                test=False)).cuda().train()
+
+    # dpt_forward_window on the prefill
+    for env, sd in (("bandit", 1), ("darkroom", 2)):
+        dm = model(40 + sd, 256, sd).device_model()
+        for T in (1, 16, 17, 33, 128, 129, 257):
+            rs, C = np.random.RandomState(100 * sd + T), T - 1
+            data = step_data(rs, 3, C, sd, A)
+            ctx = [data[k].to(dev) for k in ("context_states", "context_actions", "context_next_states",
+                                             "context_rewards")] if C else [None] * 4
+            for mode in (0, 1):
+                out[f"forward_window {env} T{T} out_mode{mode}"] = sha(
+                    dm.forward_window(data["query_states"].to(dev), *ctx, out_mode=mode))
+    # dpt_rollout_darkroom_episode
+    dim = 5
+    for K in (2, 17, 33, 129, 257):
+        m = model(50, 256, 2).eval()
+        rs = np.random.RandomState(K)
+        goals = rs.randint(0, dim, (3, 2)).astype(np.int32)
+        perm = np.stack([rs.permutation(A) for _ in range(3)]).astype(np.int32)
+        u = rs.uniform(0, 1, (K - 1, 3))
+        for name, kw in (("greedy", dict(sample=False)), ("sampled seed", dict(sample=True, seed=9)),
+                         ("sampled uniforms", dict(sample=True, uniforms=u))):
+            for pm in (None, perm):
+                rec, ret, lg = dpt_hip.rollout_darkroom_episode(m, goals, K, dim, perm=pm, logits=True, **kw)
+                out[f"episode K{K} {name} perm{int(pm is not None)}"] = sha(
+                    rec["states"], rec["actions"], rec["rewards"], rec["targets"], lg, ret)
+    # dpt_interactive_mdp_grad through InteractiveMDPTrainer: 5 envs, K = 4
+    K, rs = 4, np.random.RandomState(60)
+    goals = rs.randint(0, dim, (5, 2)).astype(np.int32)
+    for E in (32, 18):
+        for chunk in (0, 2):  # 2: the later chunks accumulate
+            for loss in ("every", "last"):
+                t = tr.InteractiveMDPTrainer(model(61, 8, 2, E), lr=1e-3, chunk=chunk, loss=loss)
+                rec = t.step(goals, K, dim, seed=13)
+                out[f"InteractiveMDPTrainer E{E} chunk{chunk} loss {loss}"] = sha(
+                    t.blob, t.m, t.v, t.dblob, t.loss, *(rec[k] for k in sorted(rec)))
+            rec, ret = t.rollout(goals, K, dim, sample=True, seed=14)
+            out[f"InteractiveMDPTrainer E{E} chunk{chunk} rollout"] = sha(ret, *(rec[k] for k in sorted(rec)))
+    # dpt_mdp_pack and dpt_darkroom_act_step called directly: N = 3, K = 4, t = 0 and 2
+    N = 3
+    for t in (0, 2):
+        rs = np.random.RandomState(70 + t)
+        i32 = lambda v: torch.from_numpy(np.asarray(v).astype(np.int32)).to(dev)  # noqa: E731
+        states, actions = i32(rs.randint(0, dim, (N, K, 2))), i32(rs.randint(0, A, (N, K - 1)))
+        rewards, targets = i32(rs.randint(0, 2, (N, K - 1))), i32(rs.randint(0, A, (N, K)))
+        goal, perm = i32(rs.randint(0, dim, (N, 2))), i32(np.stack([rs.permutation(A) for _ in range(N)]))
+        tokens = torch.zeros((N, t + 1, 10), dtype=torch.float32, device=dev)
+        _lib.call("dpt_mdp_pack", _p(states), _p(actions), _p(rewards), N, K, t, _p(tokens), _stream())
+        out[f"mdp_pack t{t}"] = sha(tokens)
+        logits = torch.from_numpy(rs.standard_normal((N, t + 1, A)).astype(np.float32)).to(dev)
+        for sample, pm in ((0, None), (1, None), (1, perm)):
+            rec = [x.clone() for x in (states, actions, rewards, targets)]
+            nxt = torch.zeros(N, dtype=torch.int64, device=dev)
+            _lib.call("dpt_darkroom_act_step", _p(logits), N, t + 1, K, t, dim, sample, None, 17, t, 0, _p(goal),
+                      _p(pm), *(_p(x) for x in rec), _p(nxt), _stream())
+            out[f"darkroom_act_step t{t} sample{sample} perm{int(pm is not None)}"] = sha(*rec, nxt)
+    # the chains' workspace sizes (a rejected shape digests as -1)
+    for sd, fns in ((1, (("dpt_interactive_workspace_numel", ()), ("dpt_explore_workspace_numel", ()))),
+                    (2, tuple(("dpt_interactive_mdp_workspace_numel", (mode,)) for mode in sorted(tr.MDP_LOSS.values())))):
+        d = tr.desc(L, 32, sd, A, 36, 1, 1)
+        for fn, extra in fns:
+            sizes, said = [], ""
+            for K in (1, 2, 6):
+                for N in (1, 8):
+                    need = ctypes.c_int64(-1)
+                    try:
+                        _lib.call(fn, ctypes.byref(d), N, K, *extra, ctypes.byref(need))
+                    except ValueError as e:  # the explorer's K = 1: its message goes into the digest
+                        said += str(e)
+                    sizes.append(need.value)
+            out[f"{fn} {extra} K 1,2,6 x N 1,8"] = sha(torch.tensor(sizes, dtype=torch.int64),
+                                                         torch.tensor(list(said.encode()), dtype=torch.uint8))
 
 
 def image_arrays(rs, n, H, sd, A):
@@ -281,7 +374,55 @@ def train_child(lib):
         b.record()
         torch.cuda.synchronize()
         ms[name] = a.elapsed_time(b) / steps
-    print(json.dumps({"lib": lib, "digests": digests, "ms": ms, "host_us": host_us_per_step(tr)}))
+    print(json.dumps({"lib": lib, "digests": digests, "ms": ms, "host_us": host_us_per_step(tr),
+                      "ms_per_call": window_ms(tr)}))
+
+
+def window_ms(tr):
+    """{case: ms per call between device events} of the width-32 window forward and what runs it or beside it,
+    four layers, 1024 sequences / envs: dpt_forward_window at windows 101, 201 and 501 (the prefill's 4-, 8- and
+    16-wave geometries), the episode rollout at the shapes of scripts/episode_rollout_ab.py and
+    InteractiveMDPTrainer.step at those of scripts/interactive_darkroom_ab.py (dim 10)."""
+    import torch
+    import dpt_hip
+    from envs.gpu_darkroom_env import GPUDarkroomEnv
+    from models.net import Transformer
+    dev, n, A, dim, out = dpt_hip.device(), 1024, 5, 10, {}
+
+    def model(H):
+        torch.manual_seed(H)
+        return Transformer(dict(horizon=H, state_dim=2, action_dim=A, n_layer=4, n_embd=32, n_head=1, dropout=0.0,
+                                test=True)).to(dev)
+
+    def timed(fn, calls, warmup=2):
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(calls):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / calls
+
+    dm = model(500).eval().device_model()
+    for T in (101, 201, 501):
+        data = step_data(np.random.RandomState(T), n, T - 1, 2, A)
+        q, *ctx = (data[k].to(dev) for k in ("query_states", "context_states", "context_actions",
+                                             "context_next_states", "context_rewards"))
+        out[f"forward_window T{T}"] = timed(lambda: dm.forward_window(q, *ctx), 30)
+    for K, mdp_calls in ((25, {"every": 8, "last": 20}), (100, {"every": 3, "last": 8})):
+        m = model(K).eval()
+        torch.manual_seed(K)
+        goals = GPUDarkroomEnv(dim, n, K, dev).goals
+        for name, sample in (("greedy", False), ("sampled", True)):
+            out[f"episode K{K} {name}"] = timed(
+                lambda: dpt_hip.rollout_darkroom_episode(m, goals, K, dim, sample=sample, seed=1), 30)
+        for mode, calls in mdp_calls.items():
+            t = tr.InteractiveMDPTrainer(model(K), lr=1e-3, weight_decay=1e-4, loss=mode)
+            out[f"interactive_mdp K{K} {mode}"] = timed(lambda: t.step(goals, K, dim, seed=1), calls, warmup=1)
+    return out
 
 
 def host_us_per_step(tr, steps=200):
@@ -321,28 +462,33 @@ def train_parent(libs):
     """Alternating rounds of train_child; one summary line, digests.txt and ab.json under AB_OUT."""
     rounds, dig = {lib: [] for lib in libs}, {}
     same = True
+    figures = ("ms_per_step", "host_us_per_step", "ms_per_call")
+    digest_rounds = int(os.environ.get("AB_DIGEST_ROUNDS", "1000000"))  # the digests in the first rounds alone
     for rnd in range(int(os.environ.get("AB_ROUNDS", "2"))):
         for lib in libs:
+            env = dict(os.environ, AB_DIGEST=os.environ.get("AB_DIGEST", "1") if rnd < digest_rounds else "0")
             cp = subprocess.run([sys.executable, __file__, "--child", lib], capture_output=True, text=True,
-                                timeout=300)
+                                timeout=300, env=env)
             if cp.returncode:
                 sys.exit(f"{lib}: child failed ({cp.returncode})\n{cp.stderr[-3000:]}")
             d = json.loads(cp.stdout.strip().splitlines()[-1])
-            rounds[lib].append({"ms_per_step": d["ms"], "host_us_per_step": d["host_us"]})
+            rounds[lib].append({"ms_per_step": d["ms"], "host_us_per_step": d["host_us"],
+                                "ms_per_call": d["ms_per_call"]})
             print(f"round {rnd} {lib}: {rounds[lib][-1]}", file=sys.stderr, flush=True)
-            same = same and dig.setdefault(lib, d["digests"]) == d["digests"]  # the same library, run to run
+            if rnd < digest_rounds:
+                same = same and dig.setdefault(lib, d["digests"]) == d["digests"]  # the same library, run to run
     ref = dig[libs[0]]
     diff = sorted(k for lib in libs for k in set(ref) | set(dig[lib]) if ref.get(k) != dig[lib].get(k))
     res = {"digest_cases": len(ref), "digests_equal": same and not diff, "differing": diff,
-           "steps_per_round": int(os.environ.get("AB_STEPS", "300")), "ms_per_step": {}, "host_us_per_step": {}}
+           "steps_per_round": int(os.environ.get("AB_STEPS", "300")), **{what: {} for what in figures}}
     for lib, rs_ in rounds.items():
-        for what in ("ms_per_step", "host_us_per_step"):
+        for what in figures:
             per = {k: [r[what][k] for r in rs_] for k in rs_[0][what]}
             res[what][lib] = {k: {"rounds": [round(x, 5) for x in v], "median": float(np.median(v)), "min": min(v),
                                   "max": max(v)} for k, v in per.items()}
     # every later argument against the first: its median may exceed the first's by the first's own spread
     res["over_margin"] = [
-        f"{what} {k} {lib}" for what in ("ms_per_step", "host_us_per_step") for lib in libs[1:]
+        f"{what} {k} {lib}" for what in figures for lib in libs[1:]
         for k, base in res[what][libs[0]].items()
         if res[what][lib][k]["median"] - base["median"] > base["max"] - base["min"]]
     out = os.environ.get("AB_OUT", os.path.join(ROOT, "profiles", "train_refactor"))

@@ -175,14 +175,20 @@ def test_host_validation_without_a_device():
 def test_python_entry_point_and_sources():
     import dpt_hip
     assert callable(dpt_hip.rollout_darkroom_episode)
-    src = open(ROOT + "/decision-pretrained-transformer_amd/csrc/dpt_prefill.hip").read()
-    assert "rollout_darkroom_episode_kernel" in src and "select_fixed_fast<kEpA>" in src
-    assert "darkroom_move(" in src and "darkroom_opt(" in src and "hipMalloc" not in src
+    csrc = ROOT + "/decision-pretrained-transformer_amd/csrc/"
+    src = open(csrc + "dpt_prefill.hip").read()
+    # the kernel steps its env by darkroom_act, the one act rule (dpt_darkroom_env.h), which selects by
+    # select_fixed_fast over the 5 DarkRoom actions and moves and labels by darkroom_move / darkroom_opt
+    rule = open(csrc + "dpt_darkroom_env.h").read()
+    rule = rule[rule.index("darkroom_act("):]
+    assert "rollout_darkroom_episode_kernel" in src and "darkroom_act(" in src
+    assert "select_fixed_fast<kDarkroomA>" in rule and "kDarkroomA = 5" in open(csrc + "dpt_darkroom_env.h").read()
+    assert "darkroom_move(" in rule and "darkroom_opt(" in rule and "hipMalloc" not in src
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_episode_kernels_spill_no_more_than_their_prefill_kernels(tmp_path):
-    """the scratch bar: the kernel restates prefill_kernel<NW>'s loop body, so each instantiation uses no more
+    """the scratch bar: the kernel runs prefill_kernel<NW>'s forward (the shared pieces), so each instantiation uses no more
     scratch bytes per lane than prefill_kernel of the same NW (more would be the step loop costing registers),
     and keeps its occupancy"""
     r = remarks("dpt_prefill.hip", tmp_path)
