@@ -31,61 +31,6 @@ int check_hip(hipError_t e, const char* what) {
     return DPT_EHIP;
 }
 
-// declared in the kernel translation units
-ModelView make_view(const float* blob, const dpt_model_desc& d);
-int64_t weights_numel(const dpt_model_desc& d);
-int launch_decode_step(const ModelView&, float*, int, int, int, const float*, float*, hipStream_t);
-int launch_window_decode(const ModelView&, float*, int, int, const float*, const float*, const float*,
-                         const float*, const float*, int, float*, hipStream_t);
-int launch_rollout_bandit(const ModelView&, const dpt_bandit_rollout_args&, hipStream_t);
-int launch_bandit_step(const double*, int, int, const int32_t*, int, double, const double*, uint64_t, uint64_t,
-                       int64_t, double*, double*, hipStream_t);
-int launch_darkroom_step(const int32_t*, const int32_t*, const int32_t*, const int32_t*, int, int, int32_t*,
-                         int32_t*, hipStream_t);
-int launch_darkroom_opt(const int32_t*, const int32_t*, const int32_t*, int, int32_t*, hipStream_t);
-int launch_select(const float*, int, int, int, float, const double*, uint64_t, uint64_t, int64_t, int32_t*,
-                  hipStream_t);
-int launch_draw(int, uint64_t, uint64_t, int64_t, int, uint32_t, double*, hipStream_t);
-int launch_rollin_bandit(const double*, const double*, int, int, int, int, double, const double*, const double*,
-                         uint64_t, int64_t, int32_t*, double*, hipStream_t);
-int launch_rollin_darkroom(const int32_t*, const int32_t*, int, int, int, int, const int32_t*, const int32_t*,
-                           uint64_t, int64_t, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*,
-                           hipStream_t);
-int launch_rollout_policy(const dpt_policy_rollout_args&, hipStream_t);
-int set_policy_wave(int on);
-int launch_pack_fragments(const ModelView&, float*, hipStream_t);
-int64_t fragments_numel(int n_layer);
-int launch_derive_l0(const ModelView&, float*, hipStream_t);
-int64_t l0_numel(int n_layer);
-int launch_rollout_darkroom(const ModelView&, const float*, const dpt_darkroom_rollout_args&, hipStream_t);
-int darkroom_max_window();
-int64_t darkroom_workspace_numel(int N, int64_t window);
-int prefill_max_window(const ModelView&);
-int launch_prefill(const ModelView&, const float*, const float*, const float*, const float*, const float*,
-                   const float*, int, int, int, float*, hipStream_t);
-bool darkroom_episode_fits(int n_layer, int K);
-int launch_darkroom_episode(const ModelView&, const float*, const dpt_darkroom_episode_args&, hipStream_t);
-int set_decode_tile(int);
-int set_darkroom_memo(int);
-int set_cache_budget(int64_t);
-int set_block0_mfma(int);
-int set_ycache_bits(int);
-int set_select_fast(int);
-int regret_max_steps();
-int64_t regret_workspace_numel(int N, int H);
-int launch_regret_moments(const double*, const double*, int, int, int, const double*, double*, double*, hipStream_t);
-int train_forward(const TrDims&, const float*, const float*, float*, float*, hipStream_t,
-                  const float* embeds = nullptr);
-int train_backward(const TrDims&, const float*, const float*, float*, const float*, float*, hipStream_t,
-                   float* dembeds = nullptr);
-int64_t train_workspace_numel(const TrDims&);
-int64_t train_blob_numel(const TrDims&);
-int train_dims_check(const TrDims&);
-int64_t gen_rollout_workspace_numel(const TrDims&, int, int);
-int rollout_bandit_generic(const TrDims&, const float*, const dpt_bandit_rollout_args&, hipStream_t,
-                           const GenEnvAct* env = nullptr);
-
-
 void drop_params(float p, uint32_t& thr, float& scale) {
     thr = 0u;
     scale = 1.0f;

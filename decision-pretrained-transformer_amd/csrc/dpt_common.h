@@ -325,7 +325,7 @@ __device__ inline int select_fixed_fast(const float (&lg)[NA], int sample, float
 // sum_s P_s v_s = (sum_s P_s y_s) Wv + bv.  Used by the bandit rollout
 // (dpt_decode.hip) and the MFMA window forwards (dpt_mfma_fwd.h).  All
 // matrices [in][out], E x E.
-// Dimensions of the generic-width training forward / backward (dpt_train.hip): layers, width,
+// Dimensions of the generic-width training forward / backward (dpt_train.hip) and rollout (dpt_generic.hip): layers, width,
 // token features, actions, sequences, tokens per sequence, wpe rows.
 struct TrDims {
     int L, E, F, A, B, T, npos;
@@ -371,7 +371,7 @@ int rows_linear_bwd_data(const float* dY, const float* W, int R, int IN, int OUT
 // dW (IN x OUT) | db (OUT) = nch partials of (IN + 1) * OUT floats summed in chunk order (tr_wgrad_reduce)
 int rows_reduce_parts(const float* part, int nch, int IN, int OUT, float* dW, float* db, hipStream_t st);
 
-// The env action of rollout_bandit_generic when it is not the action written into the context
+// The env action of rollout_bandit_generic (dpt_generic.hip) when it is not the action written into the context
 // (dpt_rollout_bandit_generic_env, dpt_explore.hip): the reward and arm_value_out come from it.
 struct GenEnvAct {
     const int32_t* env_actions;  // (H, N) injected, clamped to [0, A); or nullptr
@@ -423,5 +423,70 @@ __device__ inline double gaussian_reward(double mean, double var, double g) {
     double noise = __dadd_rn(0.0, __dmul_rn(var, g));
     return __dadd_rn(mean, noise);
 }
+
+// ----------------------------------------------------------------------------- across the sources
+// Every function one source defines and another calls (mostly dpt_abi.hip, the extern "C" surface),
+// declared here alone: the defining source includes this header too, so a changed signature fails to
+// compile there.  Default arguments live here.
+// dpt_decode.hip
+ModelView make_view(const float* blob, const dpt_model_desc& d);
+int64_t weights_numel(const dpt_model_desc& d);
+int launch_decode_step(const ModelView&, float*, int, int, int, const float*, float*, hipStream_t);
+int launch_window_decode(const ModelView&, float*, int, int, const float*, const float*, const float*,
+                         const float*, const float*, int, float*, hipStream_t);
+int launch_rollout_bandit(const ModelView&, const dpt_bandit_rollout_args&, hipStream_t);
+int launch_derive_l0(const ModelView&, float*, hipStream_t);
+int64_t l0_numel(int n_layer);
+int set_decode_tile(int);
+int set_cache_budget(int64_t);
+int set_block0_mfma(int);
+int set_ycache_bits(int);
+// dpt_env.hip
+int launch_bandit_step(const double*, int, int, const int32_t*, int, double, const double*, uint64_t, uint64_t,
+                       int64_t, double*, double*, hipStream_t);
+int launch_darkroom_step(const int32_t*, const int32_t*, const int32_t*, const int32_t*, int, int, int32_t*,
+                         int32_t*, hipStream_t);
+int launch_darkroom_opt(const int32_t*, const int32_t*, const int32_t*, int, int32_t*, hipStream_t);
+int launch_select(const float*, int, int, int, float, const double*, uint64_t, uint64_t, int64_t, int32_t*,
+                  hipStream_t);
+int launch_draw(int, uint64_t, uint64_t, int64_t, int, uint32_t, double*, hipStream_t);
+int launch_rollin_bandit(const double*, const double*, int, int, int, int, double, const double*, const double*,
+                         uint64_t, int64_t, int32_t*, double*, hipStream_t);
+int launch_rollin_darkroom(const int32_t*, const int32_t*, int, int, int, int, const int32_t*, const int32_t*,
+                           uint64_t, int64_t, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*,
+                           hipStream_t);
+int set_select_fast(int);
+// dpt_policies.hip
+int launch_rollout_policy(const dpt_policy_rollout_args&, hipStream_t);
+int set_policy_wave(int on);
+// dpt_darkroom.hip
+int launch_pack_fragments(const ModelView&, float*, hipStream_t);
+int64_t fragments_numel(int n_layer);
+int launch_rollout_darkroom(const ModelView&, const float*, const dpt_darkroom_rollout_args&, hipStream_t);
+int darkroom_max_window();
+int64_t darkroom_workspace_numel(int N, int64_t window);
+int set_darkroom_memo(int);
+// dpt_prefill.hip
+int prefill_max_window(const ModelView&);
+int launch_prefill(const ModelView&, const float*, const float*, const float*, const float*, const float*,
+                   const float*, int, int, int, float*, hipStream_t);
+bool darkroom_episode_fits(int n_layer, int K);
+int launch_darkroom_episode(const ModelView&, const float*, const dpt_darkroom_episode_args&, hipStream_t);
+// dpt_stats.hip
+int regret_max_steps();
+int64_t regret_workspace_numel(int N, int H);
+int launch_regret_moments(const double*, const double*, int, int, int, const double*, double*, double*, hipStream_t);
+// dpt_train.hip; embeds / dembeds: the token embedding computed by the caller, and its gradient
+int train_forward(const TrDims&, const float* blob, const float* tok, float* ws, float* preds, hipStream_t,
+                  const float* embeds = nullptr);
+int train_backward(const TrDims&, const float* blob, const float* tok, float* ws, const float* dpreds, float* dblob,
+                   hipStream_t, float* dembeds = nullptr);
+int64_t train_workspace_numel(const TrDims&);
+int64_t train_blob_numel(const TrDims&);
+int train_dims_check(const TrDims&);
+// dpt_generic.hip; env: the env action when it is not the selected one (nullptr: it is)
+int64_t gen_rollout_workspace_numel(const TrDims&, int N, int H);
+int rollout_bandit_generic(const TrDims&, const float* blob, const dpt_bandit_rollout_args&, hipStream_t,
+                           const GenEnvAct* env = nullptr);
 
 }  // namespace dpt

@@ -19,8 +19,8 @@
 //                 tr_wgrad_reduce: bit-identical across calls, no float atomics.
 //
 // The rest (embed_transition, embed_ln, the fc weight gradient) are the training row kernels of
-// dpt_train.hip (rows_* in dpt_common.h).  A ReLU's gradient is taken where the saved activation is
-// > 0 (torch's convention at 0).  The encoder dropout's mask is regenerated in the backward from the
+// dpt_train.hip (rows_* in dpt_common.h; dpt_generic.hip's rollout drives the same kernels through
+// dpt_rows.h).  A ReLU's gradient is taken where the saved activation is > 0 (torch's convention at 0).  The encoder dropout's mask is regenerated in the backward from the
 // desc (site DPT_SITE_IMAGE_ENC), never stored; the workspace keeps the DROPPED conv2 activations,
 // which are the fc product's input and are > 0 exactly where the ReLU passed and the mask kept.
 #include <algorithm>

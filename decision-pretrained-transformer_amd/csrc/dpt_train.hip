@@ -10,57 +10,23 @@
 //   backward: dL/dpreds -> every parameter's gradient in the packed blob layout of dpt_hip.h,
 //             with fixed-order (deterministic) reductions over the B*T rows.
 //
-// The kernels are plain row / element kernels: at the reference's widths (E = 32, FF = 128) a
-// training step is dominated by launch count and the O(T^2) attention, not by dense products,
-// and one code path serves every width (the fused rollout kernels are specialised for E = 32).
+// The file holds the trunk twice and the host code that chooses between the two:
+//   * row / element kernels (tr_linear, tr_attn_fwd, tr_wgrad_part, ...) that serve every width and
+//     every mode, dropout included: at the reference's widths (E = 32, FF = 128) a training step is
+//     dominated by launch count and the O(T^2) attention, not by dense products;
+//   * matrix-core forms on v_mfma_f32_16x16x4_f32 (tr_mm_rows, tr_wgrad_mfma, tr_attn_*_mfma) at the
+//     widths of MmWidths without dropout, and the column-split tr_mm_rows at MmDecWidths for the
+//     decode-sized rows of the generic-width rollout.  Which widths are built is written once per
+//     family (Widths, dpt_rows.h); the predicates and the dispatch both read that list;
+//   * train_forward / train_backward, the last-position modes (tr_attn_last*), and the host entry
+//     points other sources drive: rows_* (dpt_common.h, the image front end) and layernorm /
+//     row_linear / dec_product (dpt_rows.h, the generic-width rollout of dpt_generic.hip).
 // The same forward serves dpt_forward_window for models of other widths (inference).
-#include "dpt_common.h"
+#include "dpt_rows.h"
 
 namespace dpt {
 
-constexpr int kTrThreads = 256;
 constexpr int kTrRowsPerChunk = 64;   // rows per partial of the weight-gradient reductions
-
-
-// offsets of one layer in the packed blob (dpt_hip.h: [ln1 g b][c_attn W b][c_proj W b][ln2 g b][c_fc W b][mlp.c_proj W b])
-struct TrLayer {
-    int64_t ln1_g, ln1_b, attn_w, attn_b, proj_w, proj_b, ln2_g, ln2_b, fc_w, fc_b, mp_w, mp_b;
-    __host__ __device__ static TrLayer make(int64_t base, int E) {
-        TrLayer o;
-        int64_t p = base;
-        o.ln1_g = p; p += E;
-        o.ln1_b = p; p += E;
-        o.attn_w = p; p += 3ll * E * E;
-        o.attn_b = p; p += 3 * E;
-        o.proj_w = p; p += (int64_t)E * E;
-        o.proj_b = p; p += E;
-        o.ln2_g = p; p += E;
-        o.ln2_b = p; p += E;
-        o.fc_w = p; p += 4ll * E * E;
-        o.fc_b = p; p += 4 * E;
-        o.mp_w = p; p += 4ll * E * E;
-        o.mp_b = p;
-        return o;
-    }
-};
-
-struct TrBlob {  // offsets of the model-level parameters
-    int64_t emb_w, emb_b, wpe, layers, lnf_g, lnf_b, head_w, head_b, total;
-    __host__ __device__ static TrBlob make(const TrDims& d) {
-        TrBlob b;
-        int64_t p = 0;
-        b.emb_w = p; p += (int64_t)d.F * d.E;
-        b.emb_b = p; p += d.E;
-        b.wpe = p; p += (int64_t)d.npos * d.E;
-        b.layers = p; p += d.L * d.layer_size();
-        b.lnf_g = p; p += d.E;
-        b.lnf_b = p; p += d.E;
-        b.head_w = p; p += (int64_t)d.E * d.A;
-        b.head_b = p; p += d.A;
-        b.total = p;
-        return b;
-    }
-};
 
 // Workspace (floats): the forward's saved activations, then the backward's scratch.
 struct TrWs {
@@ -70,39 +36,38 @@ struct TrWs {
     __host__ __device__ static int tpad(int T) { return (T + 3) & ~3; }
     __host__ __device__ static TrWs make(const TrDims& d) {
         TrWs w;
-        // every array starts 16-B aligned (the matrix-core kernels read rows as float4); the
-        // attention probabilities / score gradients have rows padded to a multiple of 4 (tpad)
+        // the attention probabilities / score gradients have rows padded to a multiple of 4 (tpad)
         const int64_t R = d.R(), E = d.E, TT = (int64_t)d.B * d.T * tpad(d.T);
         // forward-only: one slot per per-layer array (x ping-pongs over two), no probabilities,
         // no backward scratch
         const int64_t L = d.fwd_only ? 1 : d.L;
-        int64_t p = 0;
-        w.x = p; p += (d.fwd_only ? 2 : L + 1) * R * E; p = (p + 3) & ~3ll;
-        w.y1 = p; p += L * R * E; p = (p + 3) & ~3ll;
-        w.st1 = p; p += L * R * 2; p = (p + 3) & ~3ll;
-        w.qkv = p; p += L * R * 3 * E; p = (p + 3) & ~3ll;
-        w.P = p; p += d.fwd_only ? 0 : L * TT; p = (p + 3) & ~3ll;
-        w.o = p; p += L * R * E; p = (p + 3) & ~3ll;
-        w.x2 = p; p += L * R * E; p = (p + 3) & ~3ll;
-        w.y2 = p; p += L * R * E; p = (p + 3) & ~3ll;
-        w.st2 = p; p += L * R * 2; p = (p + 3) & ~3ll;
-        w.hpre = p; p += L * R * 4 * E; p = (p + 3) & ~3ll;
-        w.yf = p; p += R * E; p = (p + 3) & ~3ll;
-        w.stf = p; p += R * 2; p = (p + 3) & ~3ll;
+        WsCursor c;
+        w.x = c.take((d.fwd_only ? 2 : L + 1) * R * E);
+        w.y1 = c.take(L * R * E);
+        w.st1 = c.take(L * R * 2);
+        w.qkv = c.take(L * R * 3 * E);
+        w.P = c.take(d.fwd_only ? 0 : L * TT);
+        w.o = c.take(L * R * E);
+        w.x2 = c.take(L * R * E);
+        w.y2 = c.take(L * R * E);
+        w.st2 = c.take(L * R * 2);
+        w.hpre = c.take(L * R * 4 * E);
+        w.yf = c.take(R * E);
+        w.stf = c.take(R * 2);
         if (d.fwd_only) {
-            w.dx = w.dx2 = w.dqkv = w.dout = w.dh = w.dy = w.dS = w.part = w.total = p;
+            w.dx = w.dx2 = w.dqkv = w.dout = w.dh = w.dy = w.dS = w.part = w.total = c.p;
             return w;
         }
-        w.dx = p; p += R * E; p = (p + 3) & ~3ll;
-        w.dx2 = p; p += R * E; p = (p + 3) & ~3ll;
-        w.dqkv = p; p += R * 3 * E; p = (p + 3) & ~3ll;
-        w.dout = p; p += R * E; p = (p + 3) & ~3ll;
-        w.dh = p; p += R * 4 * E; p = (p + 3) & ~3ll;
-        w.dy = p; p += R * E; p = (p + 3) & ~3ll;
-        w.dS = p; p += TT; p = (p + 3) & ~3ll;
+        w.dx = c.take(R * E);
+        w.dx2 = c.take(R * E);
+        w.dqkv = c.take(R * 3 * E);
+        w.dout = c.take(R * E);
+        w.dh = c.take(R * 4 * E);
+        w.dy = c.take(R * E);
+        w.dS = c.take(TT);
         const int64_t wmax = std::max<int64_t>(4 * E * E + 4 * E, (int64_t)(d.F + 1) * E);
-        w.part = p; p += nchunks(d) * std::max<int64_t>(wmax, (int64_t)(E + 1) * d.A); p = (p + 3) & ~3ll;
-        w.total = p;
+        w.part = c.take(nchunks(d) * std::max<int64_t>(wmax, (int64_t)(E + 1) * d.A));
+        w.total = c.p;
         return w;
     }
 };
@@ -116,33 +81,13 @@ __device__ inline float tr_gelu_grad(float x) {
     return 0.5f * (1.0f + th) + 0.5f * x * (1.0f - th * th) * c * (1.0f + 3.0f * a * x * x);
 }
 
-// order this wave's LDS writes before its later LDS reads of other lanes' entries
-__device__ inline void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-
 // x[r][e] = embed_transition(tok[r]) + wpe[t]   (models/net.py:52-54 + GPT2Model inputs_embeds + wpe)
 __global__ void tr_embed(const float* __restrict__ tok, const float* __restrict__ blob, TrDims d, TrBlob b,
                          float* __restrict__ x) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)d.R() * d.E) return;
-    const int r = (int)(i / d.E), e = (int)(i % d.E), t = r % d.T;
-    float acc = blob[b.emb_b + e];
-    for (int f = 0; f < d.F; ++f) acc = fmaf(tok[(int64_t)r * d.F + f], blob[b.emb_w + (int64_t)f * d.E + e], acc);
-    x[i] = acc + blob[b.wpe + (int64_t)t * d.E + e];
+    const int r = (int)(i / d.E);
+    x[i] = embed_row(tok + (int64_t)r * d.F, blob, d, b, r % d.T, (int)(i % d.E));
 }
 
 // (tr_keep, the dropout factor of one element of a site, lives in dpt_common.h)
@@ -225,23 +170,16 @@ __global__ void tr_layernorm_rows(const float* __restrict__ x, const float* __re
 }
 
 // LayerNorm of R rows: the row-group kernel where E and the pointers allow float4 rows, else tr_layernorm
-static void layernorm(const float* x, const float* g, const float* bb, int R, int E, float* y, float* st,
-                      hipStream_t s) {
+void layernorm(const float* x, const float* g, const float* bb, int R, int E, float* y, float* st, hipStream_t s) {
     const int wpb = kTrThreads / 64;
-    if (E % 4 == 0 && E <= 256 && !(((uintptr_t)x | (uintptr_t)y) & 15)) {
-        int lpr = 1;
-        while (lpr < E / 4) lpr <<= 1;
-        const unsigned blocks = (unsigned)((R + (int64_t)wpb * (64 / lpr) - 1) / ((int64_t)wpb * (64 / lpr)));
-        switch (lpr) {
-            case 1: hipLaunchKernelGGL(tr_layernorm_rows<1>, dim3(blocks), dim3(kTrThreads), 0, s, x, g, bb, R, E, y, st); return;
-            case 2: hipLaunchKernelGGL(tr_layernorm_rows<2>, dim3(blocks), dim3(kTrThreads), 0, s, x, g, bb, R, E, y, st); return;
-            case 4: hipLaunchKernelGGL(tr_layernorm_rows<4>, dim3(blocks), dim3(kTrThreads), 0, s, x, g, bb, R, E, y, st); return;
-            case 8: hipLaunchKernelGGL(tr_layernorm_rows<8>, dim3(blocks), dim3(kTrThreads), 0, s, x, g, bb, R, E, y, st); return;
-            case 16: hipLaunchKernelGGL(tr_layernorm_rows<16>, dim3(blocks), dim3(kTrThreads), 0, s, x, g, bb, R, E, y, st); return;
-            case 32: hipLaunchKernelGGL(tr_layernorm_rows<32>, dim3(blocks), dim3(kTrThreads), 0, s, x, g, bb, R, E, y, st); return;
-            default: hipLaunchKernelGGL(tr_layernorm_rows<64>, dim3(blocks), dim3(kTrThreads), 0, s, x, g, bb, R, E, y, st); return;
-        }
-    }
+    if (E % 4 == 0 && E <= 256 && !(((uintptr_t)x | (uintptr_t)y) & 15) &&
+        Pow2To64::call(pow2_ceil(E / 4), [&](auto lpr) {
+            constexpr int LPR = decltype(lpr)::value;
+            const int64_t rows = (int64_t)wpb * (64 / LPR);
+            hipLaunchKernelGGL(tr_layernorm_rows<LPR>, dim3((unsigned)((R + rows - 1) / rows)), dim3(kTrThreads), 0, s, x, g,
+                               bb, R, E, y, st);
+        }))
+        return;
     hipLaunchKernelGGL(tr_layernorm, dim3((R + wpb - 1) / wpb), dim3(kTrThreads), 0, s, x, g, bb, R, E, y, st);
 }
 
@@ -268,28 +206,9 @@ __global__ void tr_attn_fwd(const float* __restrict__ qkv, TrDims d, int site, f
     if (row >= d.R()) return;
     const int E = d.E, T = d.T, b = row / T, t = row % T;
     float* pr = sm + (size_t)wave * (T + E);
-    float* q = pr + T;
     const float* base = qkv + (int64_t)b * T * 3 * E;
-    for (int e = lane; e < E; e += 64) q[e] = base[(int64_t)t * 3 * E + e];
-    wave_lds_sync();
-    const float scale = 1.0f / sqrtf((float)E);
-    float m = -INFINITY;
-    for (int j = lane; j <= t; j += 64) {
-        const float* k = base + (int64_t)j * 3 * E + E;
-        float s = 0.f;
-        for (int e = 0; e < E; ++e) s = fmaf(q[e], k[e], s);
-        s *= scale;
-        pr[j] = s;
-        m = fmaxf(m, s);
-    }
-    m = wave_max(m);
-    float l = 0.f;
-    for (int j = lane; j <= t; j += 64) {
-        const float p = expf(pr[j] - m);
-        pr[j] = p;
-        l += p;
-    }
-    const float inv = 1.0f / wave_sum(l);
+    const float inv = attn_row_front(
+        base + (int64_t)t * 3 * E, E, t + 1, [&](int j) { return base + (int64_t)j * 3 * E + E; }, pr + T, pr);
     float* prow = P ? P + ((int64_t)b * T + t) * T : nullptr;  // saved for the backward unless forward-only
     const int64_t mrow = ((int64_t)b * T + t) * T;
     for (int j = lane; j <= t; j += 64) {
@@ -888,8 +807,6 @@ __global__ __launch_bounds__(256) void tr_ln_param_part2(const float* __restrict
 
 // ------------------------------------------------------------------------------ host side
 
-static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kTrThreads - 1) / kTrThreads); }
-
 int train_dims_check(const TrDims& d) {
     if (d.L < 1 || d.E < 1 || d.E > 1024 || d.F < 1 || d.A < 1 || d.B < 1 || d.T < 1 || d.T > d.npos ||
         (int64_t)d.B * d.T > (1ll << 26)) {
@@ -926,9 +843,12 @@ static int ln_param_grad(const float* x, const float* stt, const float* dy, int 
 
 // ---- the row kernels as host entry points (dpt_common.h; the image front end, dpt_image.hip)
 int64_t rows_chunks(int64_t R) { return (R + kTrRowsPerChunk - 1) / kTrRowsPerChunk; }
-int rows_linear(const float* X, const float* W, const float* bias, int R, int IN, int OUT, float* Y, hipStream_t st) {
+void row_linear(const float* X, const float* W, const float* bias, int R, int IN, int OUT, float* Y, hipStream_t st) {
     hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)R * OUT)), dim3(kTrThreads), 0, st, X, W, bias,
                        (const float*)nullptr, R, IN, OUT, 0, Y);
+}
+int rows_linear(const float* X, const float* W, const float* bias, int R, int IN, int OUT, float* Y, hipStream_t st) {
+    row_linear(X, W, bias, R, IN, OUT, Y, st);
     return launched("tr_linear");
 }
 int rows_layernorm(const float* x, const float* g, const float* b, int R, int E, float* y, float* stats,
@@ -961,10 +881,10 @@ int rows_reduce_parts(const float* part, int nch, int IN, int OUT, float* dW, fl
     return launched("tr_wgrad_reduce");
 }
 
-// ---- matrix-core dispatch (widths 16, 32, 64; other widths keep the row kernels)
-static bool mm_fast(int E) { return E == 16 || E == 32 || E == 64; }
-// the forward products, then the data gradients of the first four in the same order (kMmBdQkv + kind)
-enum MmKind { kMmQkv, kMmProj, kMmFc, kMmMp, kMmU, kMmLnQkv, kMmLnFc, kMmBdQkv, kMmBdProj, kMmBdFc, kMmBdMp };
+// ---- matrix-core dispatch: the widths each family is built for, once (other widths keep the row kernels)
+using MmWidths = Widths<16, 32, 64>;              // the trunk's tr_mm_rows, tr_wgrad_mfma and tr_attn_*_mfma
+using MmDecWidths = Widths<16, 32, 48, 64, 128>;  // the column-split tr_mm_rows of the generic rollout's decode rows
+static bool mm_fast(int E) { return MmWidths::has(E); }
 // a forward product's IN and OUT in units of E, and whether GELU is applied to its input as it loads
 struct MmShape { int in, out, gelu; };
 constexpr MmShape kMmShape[] = {{1, 3, 0}, {1, 1, 0}, {1, 4, 0}, {4, 1, 1}, {1, 1, 0}, {1, 3, 0}, {1, 4, 0}};
@@ -1005,11 +925,9 @@ static void mm_kind(int kind, const float* X, const float* W, const float* bias,
         case kMmLnFc: launch_mm<E, 4 * E, false, false, kMmBias | kMmLnIn>(X, W, bias, res, aux, R, Y, st); break;
     }
 }
-static void mm(int E, int kind, const float* X, const float* W, const float* bias, const float* res, const float* aux,
-               int R, float* Y, hipStream_t st) {
-    if (E == 16) mm_kind<16>(kind, X, W, bias, res, aux, R, Y, st);
-    else if (E == 32) mm_kind<32>(kind, X, W, bias, res, aux, R, Y, st);
-    else mm_kind<64>(kind, X, W, bias, res, aux, R, Y, st);
+static int mm(int E, int kind, const float* X, const float* W, const float* bias, const float* res, const float* aux,
+              int R, float* Y, hipStream_t st) {
+    return MmWidths::run("tr_mm_rows", E, [&](auto w) { mm_kind<decltype(w)::value>(kind, X, W, bias, res, aux, R, Y, st); });
 }
 // the decode-row products of the generic rollout (R = N tasks, a few thousand rows): columns split so
 // that the R / 64 row blocks times N / NC column slices fill the chip, NC = max(16, N / 4)
@@ -1024,27 +942,24 @@ static void launch_mm_dec(const float* X, const float* W, const float* bias, con
 }
 // LayerNorm on load at the widths whose row splits into a power-of-two count of float4 chunks per lane
 // (tr_layernorm_rows' summation tree without its idle lanes)
-static bool mm_ln_in_ok(int E) { return E == 16 || E == 32 || E == 64 || E == 128; }
+constexpr bool mm_ln_in_width(int E) { return E % 16 == 0 && ((E / 16) & (E / 16 - 1)) == 0; }
+bool dec_ln_in(int E) { return MmDecWidths::has(E) && mm_ln_in_width(E); }
+// false: no such kind at this width
 template <int E>
-static void mm_dec_kind(int kind, const float* X, const float* W, const float* bias, const float* res, int R, float* Y,
-                        hipStream_t st, const float* aux = nullptr) {
-    if constexpr (E == 16 || E == 32 || E == 64 || E == 128)
-        if (kind == kMmLnFc) return launch_mm_dec<E, 4 * E, false, kMmBias | kMmLnIn>(X, W, bias, res, R, Y, st, aux);
+static bool mm_dec_kind(int kind, const float* X, const float* W, const float* bias, const float* res, int R, float* Y,
+                        hipStream_t st, const float* aux) {
     switch (kind) {
-        case kMmU: launch_mm_dec<E, E, false, kMmBias>(X, W, bias, res, R, Y, st); break;
-        case kMmProj: launch_mm_dec<E, E, false, kMmBias | kMmRes>(X, W, bias, res, R, Y, st); break;
-        case kMmFc: launch_mm_dec<E, 4 * E, false, kMmBias>(X, W, bias, res, R, Y, st); break;
-        case kMmMp: launch_mm_dec<4 * E, E, true, kMmBias | kMmRes>(X, W, bias, res, R, Y, st); break;
+        case kMmU: launch_mm_dec<E, E, false, kMmBias>(X, W, bias, res, R, Y, st); return true;
+        case kMmProj: launch_mm_dec<E, E, false, kMmBias | kMmRes>(X, W, bias, res, R, Y, st); return true;
+        case kMmFc: launch_mm_dec<E, 4 * E, false, kMmBias>(X, W, bias, res, R, Y, st); return true;
+        case kMmMp: launch_mm_dec<4 * E, E, true, kMmBias | kMmRes>(X, W, bias, res, R, Y, st); return true;
+        case kMmLnFc:
+            if constexpr (mm_ln_in_width(E)) {
+                launch_mm_dec<E, 4 * E, false, kMmBias | kMmLnIn>(X, W, bias, res, R, Y, st, aux);
+                return true;
+            }
     }
-}
-static bool mm_dec_fast(int E) { return E == 16 || E == 32 || E == 48 || E == 64 || E == 128; }
-static void mm_dec(int E, int kind, const float* X, const float* W, const float* bias, const float* res, int R,
-                   float* Y, hipStream_t st, const float* aux = nullptr) {
-    if (E == 16) mm_dec_kind<16>(kind, X, W, bias, res, R, Y, st, aux);
-    else if (E == 32) mm_dec_kind<32>(kind, X, W, bias, res, R, Y, st, aux);
-    else if (E == 48) mm_dec_kind<48>(kind, X, W, bias, res, R, Y, st, aux);
-    else if (E == 64) mm_dec_kind<64>(kind, X, W, bias, res, R, Y, st, aux);
-    else mm_dec_kind<128>(kind, X, W, bias, res, R, Y, st, aux);
+    return false;
 }
 
 template <int IN, int OUT, bool ACT>
@@ -1066,9 +981,8 @@ static void wg_kind(int kind, const float* X, const float* dY, int R, float* par
 }
 static int wgrad_fast(int E, int kind, const float* X, const float* dY, int R, int IN, int OUT, float* part, float* dW,
                       float* db, hipStream_t st) {
-    if (E == 16) wg_kind<16>(kind, X, dY, R, part, st);
-    else if (E == 32) wg_kind<32>(kind, X, dY, R, part, st);
-    else wg_kind<64>(kind, X, dY, R, part, st);
+    if (int rc = MmWidths::run("tr_wgrad_mfma", E, [&](auto w) { wg_kind<decltype(w)::value>(kind, X, dY, R, part, st); }))
+        return rc;
     const int nch = (R + kTrRowsPerChunk - 1) / kTrRowsPerChunk;
     reduce_parts(part, nch, IN, OUT, dW, db, st);
     return launched("tr_wgrad_mfma");
@@ -1078,10 +992,8 @@ template <int E>
 static void attn_fwd_e(const float* qkv, const TrDims& d, float* P, float* O, hipStream_t st) {
     hipLaunchKernelGGL(tr_attn_fwd_mfma<E>, dim3(d.B, (d.T + 63) / 64), dim3(256), 0, st, qkv, d, P, O);
 }
-static void attn_fwd_fast(int E, const float* qkv, const TrDims& d, float* P, float* O, hipStream_t st) {
-    if (E == 16) attn_fwd_e<16>(qkv, d, P, O, st);
-    else if (E == 32) attn_fwd_e<32>(qkv, d, P, O, st);
-    else attn_fwd_e<64>(qkv, d, P, O, st);
+static int attn_fwd_fast(int E, const float* qkv, const TrDims& d, float* P, float* O, hipStream_t st) {
+    return MmWidths::run("tr_attn_fwd_mfma", E, [&](auto w) { attn_fwd_e<decltype(w)::value>(qkv, d, P, O, st); });
 }
 template <int E>
 static void attn_bwd_e(const float* qkv, const float* P, const float* O, const float* dO, const TrDims& d, float* dS,
@@ -1090,15 +1002,16 @@ static void attn_bwd_e(const float* qkv, const float* P, const float* O, const f
     hipLaunchKernelGGL(tr_attn_bwd_dq_mfma<E>, grid, dim3(256), 0, st, qkv, P, O, dO, d, dS, dqkv);
     hipLaunchKernelGGL(tr_attn_bwd_dkv_mfma<E>, grid, dim3(256), 0, st, qkv, P, dS, dO, d, dqkv);
 }
-static void attn_bwd_fast(int E, const float* qkv, const float* P, const float* O, const float* dO, const TrDims& d,
-                          float* dS, float* dqkv, hipStream_t st) {
-    if (E == 16) attn_bwd_e<16>(qkv, P, O, dO, d, dS, dqkv, st);
-    else if (E == 32) attn_bwd_e<32>(qkv, P, O, dO, d, dS, dqkv, st);
-    else attn_bwd_e<64>(qkv, P, O, dO, d, dS, dqkv, st);
+static int attn_bwd_fast(int E, const float* qkv, const float* P, const float* O, const float* dO, const TrDims& d,
+                         float* dS, float* dqkv, hipStream_t st) {
+    return MmWidths::run("tr_attn_bwd_mfma", E,
+                         [&](auto w) { attn_bwd_e<decltype(w)::value>(qkv, P, O, dO, d, dS, dqkv, st); });
 }
 
 // DPT_TRAIN_LAST_ONLY: the last block for the last position of each sequence alone.  One wave per
-// sequence: the causal row of query T-1 over all T keys (tr_attn_fwd's arithmetic for that row).
+// sequence: the causal row of query T-1 over all T keys.  tr_attn_fwd's scores and exponentials for
+// that row (attn_row_front) but not its rounding after them: the weighted sum runs on the unnormalised
+// exponentials and is scaled by 1 / sum once, where tr_attn_fwd normalises each probability first.
 __global__ void tr_attn_last(const float* __restrict__ qkv, TrDims d, float* __restrict__ O,
                              float* __restrict__ Pout) {
     extern __shared__ float sm[];
@@ -1107,28 +1020,9 @@ __global__ void tr_attn_last(const float* __restrict__ qkv, TrDims d, float* __r
     if (b >= d.B) return;
     const int T = d.T, E = d.E;
     float* pr = sm + (size_t)wave * (T + E);
-    float* q = pr + T;
     const float* base = qkv + (int64_t)b * T * 3 * E;
-    for (int e = lane; e < E; e += 64) q[e] = base[(int64_t)(T - 1) * 3 * E + e];
-    wave_lds_sync();
-    const float scale = 1.0f / sqrtf((float)E);
-    float m = -INFINITY;
-    for (int j = lane; j < T; j += 64) {
-        const float* k = base + (int64_t)j * 3 * E + E;
-        float s = 0.f;
-        for (int e = 0; e < E; ++e) s = fmaf(q[e], k[e], s);
-        s *= scale;
-        pr[j] = s;
-        m = fmaxf(m, s);
-    }
-    m = wave_max(m);
-    float l = 0.f;
-    for (int j = lane; j < T; j += 64) {
-        const float p = expf(pr[j] - m);
-        pr[j] = p;
-        l += p;
-    }
-    const float inv = 1.0f / wave_sum(l);
+    const float inv = attn_row_front(
+        base + (int64_t)(T - 1) * 3 * E, E, T, [&](int j) { return base + (int64_t)j * 3 * E + E; }, pr + T, pr);
     if (Pout)  // DPT_TRAIN_LAST_LOSS: the row's probabilities [B][T] for tr_attn_last_bwd
         for (int j = lane; j < T; j += 64) Pout[(int64_t)b * T + j] = pr[j] * inv;
     wave_lds_sync();
@@ -1215,19 +1109,33 @@ static void row_product(int E, int kind, const float* X, const float* W, const f
 }
 // ... or the matrix-core form when `fast` (aux = ln_g for the LayerNorm-on-load kinds, which exist in that
 // form alone), ...
-static void fwd_product(int E, int kind, bool fast, const float* X, const float* W, const float* bias,
-                        const float* res, int R, float* Y, hipStream_t st, const float* aux = nullptr) {
-    if (fast) mm(E, kind, X, W, bias, res, aux, R, Y, st);
-    else row_product(E, kind, X, W, bias, res, R, Y, st);
+static int fwd_product(int E, int kind, bool fast, const float* X, const float* W, const float* bias,
+                       const float* res, int R, float* Y, hipStream_t st, const float* aux = nullptr) {
+    if (fast) return mm(E, kind, X, W, bias, res, aux, R, Y, st);
+    row_product(E, kind, X, W, bias, res, R, Y, st);
+    return DPT_OK;
 }
 // ... and with dropout on the way to the residual (site >= 0: never `fast`, the matrix-core forms fuse the
 // residual add and take no mask): Y = res + drop(act(X) W + bias)
-static void fwd_product_res(const TrDims& d, int kind, bool fast, const float* X, const float* W, const float* bias,
-                            const float* res, int R, float* Y, int site, hipStream_t st) {
-    fwd_product(d.E, kind, fast, X, W, bias, site >= 0 ? nullptr : res, R, Y, st);
+static int fwd_product_res(const TrDims& d, int kind, bool fast, const float* X, const float* W, const float* bias,
+                           const float* res, int R, float* Y, int site, hipStream_t st) {
+    if (int rc = fwd_product(d.E, kind, fast, X, W, bias, site >= 0 ? nullptr : res, R, Y, st)) return rc;
     if (site >= 0)
         hipLaunchKernelGGL(tr_dropout, dim3(blocks_for((int64_t)R * d.E)), dim3(kTrThreads), 0, st, Y, res,
                            (int64_t)R * d.E, d, site, Y);
+    return DPT_OK;
+}
+// The generic rollout's product on R decode-sized rows (dpt_rows.h): the column-split form at MmDecWidths,
+// else the row kernel (which has no LayerNorm on load)
+int dec_product(int E, int kind, const float* X, const float* W, const float* bias, const float* res, int R, float* Y,
+                hipStream_t st, const float* aux) {
+    bool built = false;
+    if (!MmDecWidths::call(E, [&](auto w) { built = mm_dec_kind<decltype(w)::value>(kind, X, W, bias, res, R, Y, st, aux); }) &&
+        kind != kMmLnFc) {
+        row_product(E, kind, X, W, bias, res, R, Y, st);
+        built = true;
+    }
+    return built ? DPT_OK : no_width("decode-row product", E);
 }
 // The backward of forward product `kind` on R rows: the weight gradient of (X, dY) with its reduction into
 // dW | db, then the data gradient dX = dY W^T (kMmMp: times gelu'(X), X = hpre)
@@ -1238,7 +1146,7 @@ static int bwd_product(int E, int kind, bool fast, const float* X, const float* 
     const float* hpre = k.gelu ? X : nullptr;
     if (fast) {
         if (int rc = wgrad_fast(E, kind, X, dY, R, IN, OUT, part, dW, db, st)) return rc;
-        mm(E, kMmBdQkv + kind, dY, W, nullptr, nullptr, hpre, R, dX, st);
+        if (int rc = mm(E, kMmBdQkv + kind, dY, W, nullptr, nullptr, hpre, R, dX, st)) return rc;
     } else {
         if (int rc = wgrad(X, dY, R, IN, OUT, k.gelu, part, dW, db, st)) return rc;
         hipLaunchKernelGGL(tr_linear_bwd_data, dim3(blocks_for((int64_t)R * IN)), dim3(kTrThreads), 0, st, dY, W, R, IN,
@@ -1305,26 +1213,30 @@ int train_forward(const TrDims& d, const float* blob, const float* tok, float* w
         // top: [B][E] the last rows of x, the c_proj residual (LAST_LOSS: backward scratch, free in the forward)
         float* xl = last_loss ? ws + W.dx : ws + W.y2;
         if (!ln_in) layernorm(x, blob + P.ln1_g, blob + P.ln1_b, R, E, y1, st1, st);
-        fwd_product(E, ln_in ? kMmLnQkv : kMmQkv, fast, ln_in ? x : y1, blob + P.attn_w, blob + P.attn_b, nullptr, R, qkv,
-                    st, ln_in ? blob + P.ln1_g : nullptr);
+        if (int rc = fwd_product(E, ln_in ? kMmLnQkv : kMmQkv, fast, ln_in ? x : y1, blob + P.attn_w, blob + P.attn_b,
+                                 nullptr, R, qkv, st, ln_in ? blob + P.ln1_g : nullptr))
+            return rc;
         if (top) {
             if (attn_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)tr_attn_last, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds);
             hipLaunchKernelGGL(tr_attn_last, dim3((Bn + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), attn_lds,
                                st, qkv, d, o, Pm);
             hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, x, xl, Bn, d.T, E, 0);
         } else if (fast) {
-            attn_fwd_fast(E, qkv, d, Pm, o, st);
+            if (int rc = attn_fwd_fast(E, qkv, d, Pm, o, st)) return rc;
         } else {
             hipLaunchKernelGGL(tr_attn_fwd, dim3((R + rows_per_block - 1) / rows_per_block), dim3(kTrThreads), attn_lds,
                                st, qkv, d, drop ? 1 + 3 * l : -1, Pm, o);
         }
         // x2 = x + drop(o W_proj + b_proj), x_{l+1} = x2 + drop(gelu(hpre) W_mp + b_mp)
-        fwd_product_res(d, kMmProj, fast, o, blob + P.proj_w, blob + P.proj_b, top ? xl : x, Rn, x2, drop ? 2 + 3 * l : -1,
-                        st);
+        if (int rc = fwd_product_res(d, kMmProj, fast, o, blob + P.proj_w, blob + P.proj_b, top ? xl : x, Rn, x2,
+                                     drop ? 2 + 3 * l : -1, st))
+            return rc;
         if (!ln_in) layernorm(x2, blob + P.ln2_g, blob + P.ln2_b, Rn, E, y2, st2, st);
-        fwd_product(E, ln_in ? kMmLnFc : kMmFc, fast, ln_in ? x2 : y2, blob + P.fc_w, blob + P.fc_b, nullptr, Rn, hpre, st,
-                    ln_in ? blob + P.ln2_g : nullptr);
-        fwd_product_res(d, kMmMp, fast, hpre, blob + P.mp_w, blob + P.mp_b, x2, Rn, xn, drop ? 3 + 3 * l : -1, st);
+        if (int rc = fwd_product(E, ln_in ? kMmLnFc : kMmFc, fast, ln_in ? x2 : y2, blob + P.fc_w, blob + P.fc_b, nullptr, Rn,
+                                 hpre, st, ln_in ? blob + P.ln2_g : nullptr))
+            return rc;
+        if (int rc = fwd_product_res(d, kMmMp, fast, hpre, blob + P.mp_w, blob + P.mp_b, x2, Rn, xn, drop ? 3 + 3 * l : -1, st))
+            return rc;
         if (int rc = launched("train forward layer")) return rc;
     }
     // ln_f and the head; after a last-position block on its [B] rows, into [B][A] scratch (LAST_LOSS: W.dh, as
@@ -1332,8 +1244,7 @@ int train_forward(const TrDims& d, const float* blob, const float* tok, float* w
     const int Rh = last ? Bn : R;
     float* pl = !last ? preds : last_loss ? ws + W.dh : ws + W.hpre + 4 * BE;
     layernorm(ws + W.x + xs(d.L) * RE, blob + B.lnf_g, blob + B.lnf_b, Rh, E, ws + W.yf, ws + W.stf, st);
-    hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)Rh * d.A)), dim3(kTrThreads), 0, st, ws + W.yf,
-                       blob + B.head_w, blob + B.head_b, nullptr, Rh, E, d.A, 0, pl);
+    row_linear(ws + W.yf, blob + B.head_w, blob + B.head_b, Rh, E, d.A, pl, st);
     if (last)
         hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for((int64_t)Bn * d.A)), dim3(kTrThreads), 0, st, pl, preds, Bn,
                            d.T, d.A, 1);
@@ -1438,7 +1349,7 @@ int train_backward(const TrDims& d, const float* blob, const float* tok, float* 
             if (int rc = check_hip(hipMemsetAsync(dx2, 0, sizeof(float) * RE, st), "dx2 memset")) return rc;
             hipLaunchKernelGGL(tr_last_rows, dim3(blocks_for(BE)), dim3(kTrThreads), 0, st, dx2n, dx2, Bn, d.T, E, 1);
         } else if (fast) {
-            attn_bwd_fast(E, qkv, Pm, o, dout, d, dS, dqkv, st);
+            if (int rc = attn_bwd_fast(E, qkv, Pm, o, dout, d, dS, dqkv, st)) return rc;
         } else {
             const int site = drop ? 1 + 3 * l : -1;
             hipLaunchKernelGGL(tr_attn_bwd_ds, row_blocks(R), dim3(kTrThreads), ds_lds, st, qkv, Pm, o, dout, d, site, dS);
@@ -1466,363 +1377,6 @@ int train_backward(const TrDims& d, const float* blob, const float* tok, float* 
     }
     hipLaunchKernelGGL(tr_wpe_grad, dim3(blocks_for((int64_t)d.T * E)), dim3(kTrThreads), 0, st, dx, d, dblob + B.wpe);
     return launched("train backward embed");
-}
-
-// ------------------------------------------------------------------------------ generic-width rollout
-// The bandit online loop (evals/eval_bandit.py:56-103: decode -> select -> env step -> append the
-// transition) at ANY width, for models the fused E = 32 kernel (dpt_decode.hip) is not built for.
-// Exact K/V-cache decode: the bandit's query token sits at position 0 and never changes, and the
-// prediction is read at the last position, so every earlier position's keys and values stay
-// valid (causal attention) and a step computes the new token only.  The cache holds each block's
-// LayerNorm output y instead of K and V (the folded attention, GenFold): half the bytes.  One pass per step over all N
-// tasks: embed, then per layer the training forward's row kernels (or their matrix-core forms at
-// widths 16 / 32 / 64) on N rows, the attention of the new token over the task's cache, ln_f and
-// the head; then selection and the env step with the draws and arithmetic of the fused kernel.
-// Folded attention (the fused kernels' algebra, dpt_decode.hip): with y_p = LN1(x_p) a block's keys
-// and values are affine in y_p, so q . k_p = u . y_p + const (u = q W_k^T = y G + g0, G = W_q W_k^T,
-// g0 = b_q W_k^T; the constant shifts every score of the row equally and cancels in the softmax) and
-// sum_p P_p v_p = (sum_p P_p y_p) W_v + b_v, so c_proj takes the attention-weighted y on
-// Wvp = W_v W_proj with bvp = b_v W_proj + b_proj.  The cache holds y alone: E floats per position
-// and layer instead of K and V's 2E.  Per layer [G | Wvp | g0 | bvp], [in][out], fp64 sums.
-struct GenFold {
-    __host__ __device__ static int64_t size(int E) { return 2ll * E * E + 2 * E; }
-};
-__global__ void gen_fold_kernel(const float* __restrict__ blob, TrDims d, TrBlob b, float* __restrict__ fold) {
-    const int E = d.E;
-    const int64_t per = GenFold::size(E), total = (int64_t)d.L * per;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int l = (int)(i / per);
-        const int64_t o = i % per;
-        const TrLayer P = TrLayer::make(b.layers + l * d.layer_size(), E);
-        const float* Wa = blob + P.attn_w;  // [E][3E]: columns q | k | v
-        const float* ba = blob + P.attn_b;
-        const float* Wp = blob + P.proj_w;  // [E][E]
-        double acc = 0.0;
-        if (o < (int64_t)E * E) {  // G[r][c] = sum_k Wq[r][k] Wk[c][k]
-            const int r = (int)(o / E), c = (int)(o % E);
-            for (int k = 0; k < E; ++k) acc += (double)Wa[(int64_t)r * 3 * E + k] * Wa[(int64_t)c * 3 * E + E + k];
-        } else if (o < 2ll * E * E) {  // Wvp[r][c] = sum_k Wv[r][k] Wp[k][c]
-            const int64_t oo = o - (int64_t)E * E;
-            const int r = (int)(oo / E), c = (int)(oo % E);
-            for (int k = 0; k < E; ++k) acc += (double)Wa[(int64_t)r * 3 * E + 2 * E + k] * Wp[(int64_t)k * E + c];
-        } else if (o < 2ll * E * E + E) {  // g0[c] = sum_k bq[k] Wk[c][k]
-            const int c = (int)(o - 2ll * E * E);
-            for (int k = 0; k < E; ++k) acc += (double)ba[k] * Wa[(int64_t)c * 3 * E + E + k];
-        } else {  // bvp[c] = sum_k bv[k] Wp[k][c] + bp[c]
-            const int c = (int)(o - 2ll * E * E - E);
-            for (int k = 0; k < E; ++k) acc += (double)ba[2 * E + k] * Wp[(int64_t)k * E + c];
-            acc += blob[P.proj_b + c];
-        }
-        fold[i] = (float)acc;
-    }
-}
-
-// Workspace (floats): the y cache [L][N][H][E], the folded weights, then per-step rows.
-struct GenWs {
-    int64_t Y, fold, x, x2, y, st, qkv, o, h, lg, tok, total;
-    static GenWs make(const TrDims& d, int N, int H) {
-        GenWs w;
-        const int64_t E = d.E, n = N, cache = (int64_t)d.L * n * H * E;
-        int64_t p = 0;
-        auto take = [&](int64_t k) { const int64_t at = p; p += k; p = (p + 3) & ~3ll; return at; };
-        w.Y = take(cache);
-        w.fold = take((int64_t)d.L * GenFold::size(d.E));
-        w.x = take(n * E);
-        w.x2 = take(n * E);
-        w.y = take(n * E);
-        w.st = take(n * 2);
-        w.qkv = take(n * 3 * E);
-        w.o = take(n * E);
-        w.h = take(n * 4 * E);
-        w.lg = take(n * d.A);
-        w.tok = take(n * d.F);
-        w.total = p;
-        return w;
-    }
-};
-
-// x[n][e] = tok[n] emb_w + emb_b + wpe[pos]: the new token of every task (tr_embed's order)
-__global__ void gen_embed(const float* __restrict__ tok, const float* __restrict__ blob, TrDims d, TrBlob b, int N,
-                          int pos, float* __restrict__ x) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * d.E) return;
-    const int n = (int)(i / d.E), e = (int)(i % d.E);
-    float acc = blob[b.emb_b + e];
-    for (int f = 0; f < d.F; ++f) acc = fmaf(tok[(int64_t)n * d.F + f], blob[b.emb_w + (int64_t)f * d.E + e], acc);
-    x[i] = acc + blob[b.wpe + (int64_t)pos * d.E + e];
-}
-
-// The folded attention (GenFold) of the new token, one wave per task: store the token's y row (yn) at
-// position pos of the task's cache (rows [pos][E] of [N][H][E]) and attend over positions 0..pos with
-// the query u -- the scores are u . y_j / sqrt(E) over the cached rows and the new position's own row
-// (read from yn itself), the output is the attention-weighted y (c_proj runs on Wvp).  tr_attn_fwd's
-// arithmetic for the causal row of the new token: lanes stride over the keys with the columns in
-// order, then over the columns with the keys in order.  LDS per wave: H + E floats.
-__global__ void gen_attn_ydecode(const float* __restrict__ u, const float* __restrict__ yn, float* __restrict__ Yc,
-                                 int E, int N, int H, int pos, float* __restrict__ O) {
-    extern __shared__ float sm[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int task = blockIdx.x * (blockDim.x / 64) + wave;
-    if (task >= N) return;
-    float* pr = sm + (size_t)wave * (H + E);
-    float* q = pr + H;
-    const float* row = yn + (int64_t)task * E;
-    float* Y = Yc + (int64_t)task * H * E;
-    for (int e = lane; e < E; e += 64) {
-        q[e] = u[(int64_t)task * E + e];
-        Y[(int64_t)pos * E + e] = row[e];
-    }
-    wave_lds_sync();
-    const float scale = 1.0f / sqrtf((float)E);
-    float m = -INFINITY;
-    for (int j = lane; j <= pos; j += 64) {
-        const float* k = j == pos ? row : Y + (int64_t)j * E;
-        float s = 0.f;
-        for (int e = 0; e < E; ++e) s = fmaf(q[e], k[e], s);
-        s *= scale;
-        pr[j] = s;
-        m = fmaxf(m, s);
-    }
-    m = wave_max(m);
-    float l = 0.f;
-    for (int j = lane; j <= pos; j += 64) {
-        const float p = expf(pr[j] - m);
-        pr[j] = p;
-        l += p;
-    }
-    const float inv = 1.0f / wave_sum(l);
-    for (int j = lane; j <= pos; j += 64) pr[j] *= inv;
-    wave_lds_sync();
-    for (int e = lane; e < E; e += 64) {
-        float acc = 0.f;
-        for (int j = 0; j < pos; ++j) acc = fmaf(pr[j], Y[(int64_t)j * E + e], acc);
-        acc = fmaf(pr[pos], row[e], acc);
-        O[(int64_t)task * E + e] = acc;
-    }
-}
-
-// The same for E % 4 == 0, E <= 256, with the rows read as float4, in one pass over the y cache (flash
-// decoding): LPK lanes per key (a power of two >= E / 4, one float4 of the row each), 64 / LPK = KPW keys
-// per wave-instruction, so every key row is one coalesced read.  Scores are 4-term partial dots summed
-// over the key's lanes by xor shuffles.  Lane group kq takes keys kq, kq + KPW, ..., kU keys of the group
-// per iteration (kU rows in flight per lane), and keeps its own softmax state (m, l, acc) in the exp2
-// domain; the KPW groups are merged at the end by xor shuffles.  Each y row is read once, for its score
-// and for the weighted sum.  A different fp32 summation order than gen_attn_ydecode (and tr_attn_fwd),
-// the same softmax.  No LDS.
-template <int LPK>
-__global__ void gen_attn_ydecode4(const float* __restrict__ u, const float* __restrict__ yn, float* __restrict__ Yc,
-                                  int E, int N, int H, int pos, float* __restrict__ O) {
-    constexpr int KPW = 64 / LPK, kU = 4;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int task = blockIdx.x * (blockDim.x / 64) + wave;
-    if (task >= N) return;
-    const int E4 = E >> 2, c = lane % LPK, kq = lane / LPK;
-    const bool act = c < E4;
-    const floatx4* Y4 = reinterpret_cast<const floatx4*>(Yc + (int64_t)task * H * E);
-    const floatx4 zero = {0.f, 0.f, 0.f, 0.f};
-    const floatx4 q = act ? reinterpret_cast<const floatx4*>(u + (int64_t)task * E)[c] : zero;
-    const floatx4 yv = act ? reinterpret_cast<const floatx4*>(yn + (int64_t)task * E)[c] : zero;
-    if (kq == 0 && act) reinterpret_cast<floatx4*>(Yc + (int64_t)task * H * E)[(int64_t)pos * E4 + c] = yv;
-    const float scale = 1.4426950408889634f / sqrtf((float)E);  // scores in the exp2 domain
-    float m = -INFINITY, l = 0.f;
-    floatx4 acc = zero;
-    for (int jb = 0; jb <= pos; jb += KPW * kU) {
-        floatx4 v[kU];
-        float sc[kU];
-#pragma unroll
-        for (int t = 0; t < kU; ++t) {
-            const int j = jb + t * KPW + kq;
-            v[t] = zero;
-            if (act && j < pos) v[t] = Y4[(int64_t)j * E4 + c];
-            else if (act && j == pos) v[t] = yv;
-        }
-        float mn = m;
-#pragma unroll
-        for (int t = 0; t < kU; ++t) {
-            const int j = jb + t * KPW + kq;
-            float d = fmaf(q[0], v[t][0], fmaf(q[1], v[t][1], fmaf(q[2], v[t][2], q[3] * v[t][3])));
-#pragma unroll
-            for (int x = 1; x < LPK; x <<= 1) d += __shfl_xor(d, x, 64);
-            sc[t] = j <= pos ? d * scale : -INFINITY;
-            mn = fmaxf(mn, sc[t]);
-        }
-        if (mn == -INFINITY) continue;  // no key of this group in the chunk yet
-        const float corr = exp2f(m - mn);  // 0 while m = -inf
-        l *= corr;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] *= corr;
-#pragma unroll
-        for (int t = 0; t < kU; ++t) {
-            const float p = exp2f(sc[t] - mn);
-            l += p;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[r] = fmaf(p, v[t][r], acc[r]);
-        }
-        m = mn;
-    }
-    // merge the KPW groups' states (every group but kq = 0 may be empty: m = -inf, l = 0)
-#pragma unroll
-    for (int x = LPK; x < 64; x <<= 1) {
-        const float mo = __shfl_xor(m, x, 64), lo = __shfl_xor(l, x, 64);
-        floatx4 ao;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ao[r] = __shfl_xor(acc[r], x, 64);
-        const float mm = fmaxf(m, mo);
-        const float ca = m == -INFINITY ? 0.f : exp2f(m - mm), cb = mo == -INFINITY ? 0.f : exp2f(mo - mm);
-        l = l * ca + lo * cb;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = acc[r] * ca + ao[r] * cb;
-        m = mm;
-    }
-    if (kq == 0 && act) reinterpret_cast<floatx4*>(O + (int64_t)task * E)[c] = acc * (1.0f / l);
-}
-
-struct GenEnv {
-    int N, H, A, sd, type, sample;
-    int64_t first_task;
-    double var;
-    uint64_t seed, counter;
-    const double* means;
-    const double* uniforms;
-    const double* noise;
-    int32_t* actions_out;
-    double* rewards_out;
-    double* arm_value_out;
-    float* logits_out;
-    GenEnvAct env;  // all zero: the env is stepped with the selected action
-};
-
-// the token rows: the query [1_sd, 0_A, 0_sd, 0] at step 0 (eval_bandit.py: query state ones)
-__global__ void gen_query_token(int N, int F, int sd, float* __restrict__ tok) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)N * F) return;
-    tok[i] = (int)(i % F) < sd ? 1.f : 0.f;
-}
-
-// selection and env step of step h for every task (the fused kernel's draws, select_from_logits
-// and reward arithmetic), the outputs, and the next token [1_sd, onehot(a), 1_sd, float(r)]
-// (eval_bandit.py:83-86)
-__global__ void gen_select_env(const float* __restrict__ lg, GenEnv g, int h, float* __restrict__ tok) {
-    const int task = blockIdx.x * blockDim.x + threadIdx.x;
-    if (task >= g.N) return;
-    const int64_t gtask = g.first_task + task;
-    const uint64_t ctr = g.counter + (uint64_t)h;
-    double u = 0.0;
-    if (g.sample) u = g.uniforms ? g.uniforms[(size_t)h * g.N + task] : philox_uniform(g.seed, ctr, gtask, DPT_STREAM_SELECT);
-    const float* l = lg + (int64_t)task * g.A;
-    const int a = select_from_logits(l, g.A, g.sample, 1.0f, u);
-    // the arm the env is stepped with: the selected one, or a separate one (injected and clamped, or uniform
-    // over the arms from its own Philox stream); `a` still goes into the records and the next token
-    int ea = a;
-    if (g.env.env_actions) ea = min(g.A - 1, max(0, g.env.env_actions[(size_t)h * g.N + task]));
-    else if (g.env.random) ea = min(g.A - 1, (int)floor(philox_uniform(g.seed, ctr, gtask, DPT_STREAM_ENVACT) * g.A));
-    const double mean = g.means[(int64_t)task * g.A + ea];
-    const bool bern = (g.type & ~DPT_BANDIT_F32) == DPT_BANDIT_BERNOULLI;
-    double dr;
-    if (g.noise) dr = g.noise[(size_t)h * g.N + task];
-    else if (bern) dr = philox_uniform(g.seed, ctr, gtask, DPT_STREAM_REWARD);
-    else dr = philox_normal(g.seed, ctr, gtask, DPT_STREAM_REWARD);
-    double r;
-    if (bern) r = dr < mean ? 1.0 : 0.0;
-    else if (g.type & DPT_BANDIT_F32)  // GPUBanditEnv's fp32 arithmetic, as bandit_step_kernel (dpt_env.hip)
-        r = (double)__fadd_rn((float)mean, __fmul_rn((float)dr, (float)g.var));
-    else r = gaussian_reward(mean, g.var, dr);
-    const size_t o = (size_t)task * g.H + h;
-    g.actions_out[o] = a;
-    g.rewards_out[o] = r;
-    g.arm_value_out[o] = mean;
-    if (g.env.env_actions_out) g.env.env_actions_out[o] = ea;
-    if (g.logits_out)
-        for (int k = 0; k < g.A; ++k) g.logits_out[((size_t)h * g.N + task) * g.A + k] = l[k];
-    const int F = 2 * g.sd + g.A + 1;
-    float* t = tok + (int64_t)task * F;
-    for (int k = 0; k < g.sd; ++k) t[k] = 1.f;
-    for (int k = 0; k < g.A; ++k) t[g.sd + k] = k == a ? 1.f : 0.f;
-    for (int k = 0; k < g.sd; ++k) t[g.sd + g.A + k] = 1.f;
-    t[F - 1] = (float)r;
-}
-
-int64_t gen_rollout_workspace_numel(const TrDims& d, int N, int H) { return GenWs::make(d, N, H).total; }
-
-int rollout_bandit_generic(const TrDims& d, const float* blob, const dpt_bandit_rollout_args& a, hipStream_t st,
-                           const GenEnvAct* env) {
-    if (int rc = train_dims_check(d)) return rc;
-    if (a.A != d.A || d.F != 2 + a.A + 1 || a.H > d.npos || a.N < 1 || a.H < 1 ||
-        ((a.type & ~DPT_BANDIT_F32) != DPT_BANDIT_GAUSSIAN && (a.type & ~DPT_BANDIT_F32) != DPT_BANDIT_BERNOULLI) ||
-        a.kvcache == nullptr || a.means == nullptr ||
-        a.actions_out == nullptr || a.rewards_out == nullptr || a.arm_value_out == nullptr) {
-        set_error(DPT_EINVAL, "generic bandit rollout: A=%d (model %d), state_dim must be 1, H=%d (n_positions %d), type=%d",
-                  a.A, d.A, a.H, d.npos, a.type);
-        return DPT_EINVAL;
-    }
-    const int N = a.N, H = a.H, E = d.E, L = d.L;
-    const TrBlob B = TrBlob::make(d);
-    const GenWs W = GenWs::make(d, N, H);
-    float* ws = a.kvcache;
-    const int rows_per_block = kTrThreads / 64;
-    const unsigned row_blocks = (N + rows_per_block - 1) / rows_per_block;
-    // the float4 attention for E % 4 == 0 up to 256 (LPK lanes per key), else the scalar one
-    using AttnKernel = void (*)(const float*, const float*, float*, int, int, int, int, float*);
-    const AttnKernel attn_k = E % 4 || E > 256 ? gen_attn_ydecode
-                              : E <= 16        ? gen_attn_ydecode4<4>
-                              : E <= 32        ? gen_attn_ydecode4<8>
-                              : E <= 64        ? gen_attn_ydecode4<16>
-                              : E <= 128       ? gen_attn_ydecode4<32>
-                                               : gen_attn_ydecode4<64>;
-    // the scalar form's dynamic LDS (the float4 form: none)
-    const size_t attn_lds = attn_k == gen_attn_ydecode ? sizeof(float) * rows_per_block * (size_t)(H + E) : 0;
-    if (attn_lds > 160 * 1024) {
-        set_error(DPT_EUNSUPPORTED, "generic bandit rollout: H=%d too long for the attention kernel", H);
-        return DPT_EUNSUPPORTED;
-    }
-    if (attn_lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds);
-    GenEnv g{N, H, a.A, 1, a.type, a.sample, a.first_task, a.var, a.seed, a.counter, a.means, a.uniforms, a.noise,
-             a.actions_out, a.rewards_out, a.arm_value_out, a.logits_out, env ? *env : GenEnvAct{nullptr, 0, nullptr}};
-    // the column-split matrix-core products (mm_dec) or the row kernels; ln_2 on load where mm_dec has it
-    // (bit-identical to the separate LayerNorm)
-    const bool fast = mm_dec_fast(E), ln_in = fast && mm_ln_in_ok(E);
-    auto product = [&](int kind, const float* X, const float* Wt, const float* bias, const float* res, float* Y,
-                       const float* aux = nullptr) {
-        if (fast) mm_dec(E, kind, X, Wt, bias, res, N, Y, st, aux);
-        else row_product(E, kind, X, Wt, bias, res, N, Y, st);
-    };
-    float* x = ws + W.x;
-    float* x2 = ws + W.x2;
-    float* y = ws + W.y;
-    float* stt = ws + W.st;
-    float* qkv = ws + W.qkv;
-    float* o = ws + W.o;
-    float* hb = ws + W.h;
-    const int64_t NE = (int64_t)N * E, cache = (int64_t)N * H * E;
-    hipLaunchKernelGGL(gen_query_token, dim3(blocks_for((int64_t)N * d.F)), dim3(kTrThreads), 0, st, N, d.F, 1,
-                       ws + W.tok);
-    hipLaunchKernelGGL(gen_fold_kernel, dim3(blocks_for((int64_t)L * GenFold::size(E))), dim3(kTrThreads), 0, st, blob, d,
-                       B, ws + W.fold);
-    for (int h = 0; h < H; ++h) {
-        hipLaunchKernelGGL(gen_embed, dim3(blocks_for(NE)), dim3(kTrThreads), 0, st, ws + W.tok, blob, d, B, N, h, x);
-        for (int l = 0; l < L; ++l) {
-            const TrLayer P = TrLayer::make(B.layers + l * d.layer_size(), E);
-            layernorm(x, blob + P.ln1_g, blob + P.ln1_b, N, E, y, stt, st);
-            // u = y G + g0, the folded attention over the y cache, c_proj on Wvp (GenFold)
-            const float* F = ws + W.fold + l * GenFold::size(E);
-            const float *G = F, *Wvp = F + (int64_t)E * E, *g0 = F + 2ll * E * E, *bvp = g0 + E;
-            float* uq = qkv;
-            product(kMmU, y, G, g0, nullptr, uq);
-            hipLaunchKernelGGL(attn_k, dim3(row_blocks), dim3(kTrThreads), attn_lds, st, uq, y, ws + W.Y + l * cache, E,
-                               N, H, h, o);
-            product(kMmProj, o, Wvp, bvp, x, x2);
-            if (!ln_in) layernorm(x2, blob + P.ln2_g, blob + P.ln2_b, N, E, y, stt, st);
-            product(ln_in ? kMmLnFc : kMmFc, ln_in ? x2 : y, blob + P.fc_w, blob + P.fc_b, nullptr, hb,
-                    ln_in ? blob + P.ln2_g : nullptr);
-            product(kMmMp, hb, blob + P.mp_w, blob + P.mp_b, x2, x);
-        }
-        layernorm(x, blob + B.lnf_g, blob + B.lnf_b, N, E, y, stt, st);
-        hipLaunchKernelGGL(tr_linear, dim3(blocks_for((int64_t)N * d.A)), dim3(kTrThreads), 0, st, y, blob + B.head_w,
-                           blob + B.head_b, nullptr, N, E, d.A, 0, ws + W.lg);
-        hipLaunchKernelGGL(gen_select_env, dim3((N + 255) / 256), dim3(256), 0, st, ws + W.lg, g, h, ws + W.tok);
-        if (int rc = launched("generic bandit rollout step")) return rc;
-    }
-    return DPT_OK;
 }
 
 }  // namespace dpt

@@ -7,7 +7,8 @@ layer-0 workspace / the logits memo (suffixes in that order: lib.so+nows+nomemo)
 (before any other suffix) loads that file in place of dpt_hip/train.py: an A/B of the Python layer on one library.
 Env: AB_H, AB_N, AB_A, AB_TILE, AB_ROUNDS.
 AB_WL=train: the training entry points instead (trunk forward / backward, generic rollout, the three
-cross-entropies, the fused steps and the four trainer classes over several steps): one sha1 per case over
+cross-entropies, the fused steps and the four trainer classes over several steps, the trunk's and the generic
+rollout's workspace sizes): one sha1 per case over
 the raw bytes of every output (group 5: the width-32 window forward, the DarkRoom episode rollout, the
 interactive DarkRoom step and the chains' workspace sizes), then the ms per dpt_train_step at the shapes of
 scripts/train_timing.py (AB_STEPS steps between device events), the host microseconds to enqueue one step of each
@@ -69,7 +70,7 @@ def train_digests():
                     out[f"trunk E{E} T{T} flags{flags} drop{p} {entry}"] = sha(*outs)
     # 2. the generic rollout past one 64-key lap
     N, H = 9, 70
-    for E in (16, 18, 48, 64, 128):
+    for E in (16, 18, 20, 32, 48, 64, 128, 256):
         for name, code in (("gaussian", _lib.BANDIT_GAUSSIAN), ("bernoulli", _lib.BANDIT_BERNOULLI)):
             rs = np.random.RandomState(7 * E + code)
             shape = SimpleNamespace(n_layer=L, n_embd=E, state_dim=1, action_dim=A, n_positions=72)
@@ -77,6 +78,18 @@ def train_digests():
             o = tr.rollout_bandit_generic(shape, rs.uniform(0, 1, (N, A)), H, 0.3, True, code, seed=11,
                                           want_logits=True, blob=blob)
             out[f"rollout E{E} {name}"] = sha(o["actions"], o["rewards"], o["logits"])
+    # the trunk's and the rollout's workspace sizes, training and forward-only
+    for E in (16, 18, 20, 32, 128):
+        sizes = []
+        for flags in (0, FO):
+            for B_, T_ in ((1, 1), (3, 65), (64, 501)):
+                sizes.append(tr._numel("dpt_train_workspace_numel", tr.desc(L, E, sd, A, 2004, B_, T_, flags=flags)))
+            for N_, H_ in ((1, 1), (9, 70), (1000, 500)):
+                need = ctypes.c_int64(-1)
+                _lib.call("dpt_rollout_bandit_generic_workspace_numel",
+                          ctypes.byref(tr.desc(L, E, sd, A, 2004, 1, 1, flags=flags)), N_, H_, ctypes.byref(need))
+                sizes.append(need.value)
+        out[f"workspace sizes E{E}"] = sha(torch.tensor(sizes, dtype=torch.int64))
     # 3. the loss kernels: one target out of range, one weight 0
     for B_, T_, A_ in ((3, 1, 5), (4, 9, 20), (2, 5, 1)):
         rs = np.random.RandomState(100 * B_ + A_)

@@ -1,5 +1,5 @@
 """The fused explorer/exploiter bandit training step (csrc/dpt_explore.hip, the separate env action
-of rollout_bandit_generic in csrc/dpt_train.hip, dpt_hip.train.ExploreExploitTrainer,
+of rollout_bandit_generic in csrc/dpt_generic.hip, dpt_hip.train.ExploreExploitTrainer,
 train_explorer_exploiter.py).
 
 The every-position cross-entropy and the advantage weights against float64 restatements; the rollout

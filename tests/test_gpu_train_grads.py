@@ -1,5 +1,5 @@
 """Every training gradient path against the float64 oracle directly (csrc/dpt_train.hip,
-dpt_trainstep.hip, dpt_interactive.hip; oracle/dpt_oracle_torch.py).
+dpt_trainstep.hip, dpt_interactive.hip, the rollout of dpt_generic.hip; oracle/dpt_oracle_torch.py).
 
 The parameter-tracking tests (test_gpu_train_step, test_gpu_interactive) see a gradient only through
 AdamW, which divides every entry by its own running magnitude: a gradient wrong by a common factor
@@ -286,12 +286,15 @@ def test_interactive_step_gradient(K, E, chunk, full_width):
 # ----------------------------------------------------------------------------- 7. decode attention past one lap
 # (E, L, N, H, draw seed): the seed is the first whose float64-oracle rollout keeps every selection
 # uniform more than 1e-5 from a cdf edge (found on the host; asserted below)
-@pytest.mark.parametrize("E,L,N,H,seed", [(16, 2, 9, 130, 0), (18, 2, 9, 130, 0), (64, 2, 9, 40, 0)])
+@pytest.mark.parametrize("E,L,N,H,seed", [(16, 2, 9, 130, 0), (18, 2, 9, 130, 0), (64, 2, 9, 40, 0),
+                                             (20, 2, 9, 70, 0), (128, 2, 9, 40, 0), (256, 1, 9, 20, 0)])
 def test_decode_attention_past_one_lap(E, L, N, H, seed):
     """dpt_rollout_bandit_generic against the float64 oracle's re-forward-every-step rollout fed the
     same draws, at horizons past one lap of the decode attention: gen_attn_ydecode (width 18, lanes
     on keys with stride 64) at 130 keys, gen_attn_ydecode4<4> (width 16, 64 keys per iteration) into
-    its second and third iteration with the running-max rescale, and width 64 at 40.  Logits within
+    its second and third iteration with the running-max rescale, and width 64 at 40; width 20
+    (gen_attn_ydecode4<8> with the row-kernel products), 128 (<32>, the column-split products with
+    LayerNorm on load) and 256 (<64>, one key per wave instruction, row-kernel products).  Logits within
     1e-5 at every step; actions, rewards and arm values exactly, no task or step left out: the draw
     seed is chosen so that the oracle alone has no uniform within 1e-5 of a cdf edge, and that margin
     is asserted here, so a changed oracle or seed fails loudly instead of flaking."""

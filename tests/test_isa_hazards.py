@@ -33,7 +33,8 @@ def file_flags(src):
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 @pytest.mark.parametrize("src", ["dpt_darkroom.hip", "dpt_prefill.hip", "dpt_decode.hip", "dpt_train.hip",
-                                 "dpt_policies.hip", "dpt_env.hip", "dpt_stats.hip", "dpt_abi.hip"])
+                                 "dpt_generic.hip", "dpt_policies.hip", "dpt_env.hip", "dpt_stats.hip",
+                                 "dpt_abi.hip"])
 def test_no_short_mfma_hazard_paths(src, tmp_path):
     import isa_hazard_cfg
     out = tmp_path / (src + ".s")
