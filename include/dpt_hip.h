@@ -14,8 +14,19 @@
  *  - Every pointer argument is a DEVICE pointer unless the name ends in _host.
  *    The caller (torch) allocates every tensor; the library allocates only the
  *    weight blob owned by an opaque dpt_model handle.
+ *  - Workspaces and outputs need no initialisation, and no result depends on
+ *    what they held before the call: every word a kernel reads from them was
+ *    written earlier in the same call (or by the documented earlier call, as
+ *    the forward's workspace handed to its backward), and every documented
+ *    output element is written.  A workspace may be reused across calls, also
+ *    with other shapes, without being cleared (tests/test_gpu_dirty_buffers.py
+ *    fills them with NaN and 3.39e38 patterns before every call).
  *  - All launches are asynchronous on the given stream (hipStream_t passed as
- *    void* so this header needs no HIP include; NULL = default stream).
+ *    void* so this header needs no HIP include; NULL = default stream).  No
+ *    entry point that takes a stream synchronises the host or touches another
+ *    stream: every launch, memset and copy of a call is ordered on that one
+ *    stream (tests/test_gpu_side_stream.py).  dpt_model_create takes none and
+ *    synchronises the device.
  *  - Return 0 (DPT_OK) or a negative DPT_E* code; dpt_last_error() returns a
  *    thread-local message for the last failing call on this thread.
  *  - Layouts are C-contiguous, row-major.  fp64 for everything the reference
