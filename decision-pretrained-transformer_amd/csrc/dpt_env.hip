@@ -6,6 +6,7 @@
 // fused inside rollout_bandit_kernel (dpt_decode.hip).
 #include "dpt_common.h"
 #include "dpt_darkroom_env.h"  // darkroom_move, darkroom_opt
+#include "dpt_rollin.h"        // the rollins' per-step draws and arithmetic (shared with dpt_fresh.hip)
 
 namespace dpt {
 
@@ -112,33 +113,11 @@ __global__ void rollin_bandit_kernel(const double* __restrict__ means, const dou
     const int i = (int)(gid / H), h = (int)(gid % H);
     const int64_t task = first_task + i;
     const double u = uniforms ? uniforms[(size_t)h * N + i] : philox_uniform(seed, h, task, DPT_STREAM_ROLLIN);
-    const double* p = probs + (size_t)i * A;
-    double total = 0.0;
-    for (int k = 0; k < A; ++k) total += p[k];
-    double c = 0.0;
-    int a = 0;
-    for (int k = 0; k < A; ++k) {
-        c += p[k];
-        a += (c / total <= u) ? 1 : 0;
-    }
-    a = a < A ? a : A - 1;
-    const double mean = means[(size_t)i * A + a];
-    double r;
-    if (type == DPT_BANDIT_BERNOULLI) {
-        const double ur = noise ? noise[(size_t)h * N + i] : philox_uniform(seed, h, task, DPT_STREAM_REWARD);
-        r = (ur < mean) ? 1.0 : 0.0;
-    } else {
-        const double g = noise ? noise[(size_t)h * N + i] : philox_normal(seed, h, task, DPT_STREAM_REWARD);
-        r = gaussian_reward(mean, var, g);
-    }
+    const int a = rollin_bandit_arm(probs + (size_t)i * A, A, u);
+    const double r = rollin_bandit_reward(type, means[(size_t)i * A + a], var, noise != nullptr,
+                                          noise ? noise[(size_t)h * N + i] : 0.0, seed, h, task);
     actions[gid] = a;
     rewards[gid] = r;
-}
-
-__device__ inline int philox_randint(uint64_t seed, uint64_t step, int64_t task, uint32_t stream, int word, int n) {
-    U4 r = philox(seed, step, task, stream);
-    const uint32_t w = word == 0 ? r.x : word == 1 ? r.y : word == 2 ? r.z : r.w;
-    return (int)(((uint64_t)w * (uint64_t)n) >> 32);  // multiply-shift, bias < n / 2^32
 }
 
 // collect_data.py:83-111 rollin_mdp + generate_mdp_histories_from_envs (:189-218).
@@ -164,11 +143,10 @@ __global__ void rollin_darkroom_kernel(const int32_t* __restrict__ goal, const i
         states[2 * o] = x;
         states[2 * o + 1] = y;
         actions[o] = a;
-        const int ea = pm ? pm[a] : a;
-        darkroom_move(x, y, ea, dim);
+        const int r = rollin_darkroom_step(x, y, a, pm, dim, gx, gy);
         next_states[2 * o] = x;
         next_states[2 * o + 1] = y;
-        rewards[o] = (x == gx && y == gy) ? 1 : 0;
+        rewards[o] = r;
     };
     if (mode == 0) {
         const int h = (int)(gid % H);
@@ -179,9 +157,7 @@ __global__ void rollin_darkroom_kernel(const int32_t* __restrict__ goal, const i
             y = states_in[2 * o + 1];
             a = actions_in[o];
         } else {
-            x = philox_randint(seed, h, task, DPT_STREAM_ROLLIN, 0, dim);
-            y = philox_randint(seed, h, task, DPT_STREAM_ROLLIN, 1, dim);
-            a = philox_randint(seed, h, task, DPT_STREAM_ROLLIN, 2, 5);
+            rollin_darkroom_draw(seed, h, task, dim, x, y, a);
         }
         emit(h, x, y, a);
     } else {
@@ -195,8 +171,8 @@ __global__ void rollin_darkroom_kernel(const int32_t* __restrict__ goal, const i
     }
     const bool lead = mode == 0 ? (gid % H == 0) : true;
     if (lead && query) {
-        const int qx = philox_randint(seed, H, task, DPT_STREAM_ROLLIN, 0, dim);
-        const int qy = philox_randint(seed, H, task, DPT_STREAM_ROLLIN, 1, dim);
+        int qx, qy;
+        rollin_darkroom_query(seed, H, task, dim, qx, qy);
         query[2 * i] = qx;
         query[2 * i + 1] = qy;
         if (opt_action) opt_action[i] = darkroom_opt(qx, qy, gx, gy, pm);

@@ -1,7 +1,8 @@
 // The training step around dpt_train_forward / dpt_train_backward (include/dpt_hip.h, "training
 // step"): batch packing from a device-resident dataset, the summed cross-entropy of train.py:295-301
 // with its gradient, AdamW over the whole packed blob, and the entry points that chain them on one
-// stream without a host synchronisation.  Nothing here allocates: every buffer is the caller's.
+// stream without a host synchronisation; the fresh-task steps are the same chain with the generator of
+// dpt_fresh.hip in place of the pack.  Nothing here allocates: every buffer is the caller's.
 //
 // Arithmetic: the cross-entropy and the AdamW update are evaluated in fp64 per element from the
 // fp32 inputs and rounded once on the store (both kernels are bound by their loads and stores, the
@@ -194,6 +195,43 @@ static int check_step_args(const dpt_train_desc* d, const dpt_train_data* data, 
     return DPT_OK;
 }
 
+// What dpt_train_step (opt given) / dpt_train_eval_loss (opt NULL) and their fresh-task twins share: the
+// workspace regions, the batch written into tokens / targets by `batch_into(run, tokens, targets)` (the
+// pack from a dataset, or the generator), then forward -> cross-entropy [-> backward -> AdamW].  The
+// workspace is laid out for desc.batch; a smaller batch uses a prefix of each region.
+template <class Batch>
+static int step_chain(const char* who, const dpt_train_desc* d, int32_t batch, const float* blob_in, float* blob,
+                      float* m, float* v, const dpt_adamw_args* opt, float* ws, double* loss_acc, void* stream,
+                      Batch batch_into) {
+    StepWs w;
+    if (int rc = step_ws(d, w)) return rc;
+    int64_t nblob = 0;
+    if (int rc = dpt_train_blob_numel(d, &nblob)) return rc;
+    DPT_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace not 16-byte aligned", who);
+    dpt_train_desc run = *d;
+    run.batch = batch;
+    if (!opt) run.reserved = DPT_TRAIN_FORWARD_ONLY;  // every position's preds: never DPT_TRAIN_LAST_ONLY
+    float *tokens = ws + w.tokens, *targets = ws + w.targets, *preds = ws + w.preds, *dpreds = ws + w.dpreds;
+    double* partial = reinterpret_cast<double*>(ws + w.partial);
+    if (int rc = batch_into(run, tokens, targets)) return rc;
+    if (int rc = dpt_train_forward(&run, blob_in, tokens, ws + w.train, preds, stream)) return rc;
+    if (int rc = dpt_train_ce_loss(preds, targets, batch, run.window, run.action_dim, opt ? dpreds : nullptr, partial,
+                                   loss_acc, stream))
+        return rc;
+    if (!opt) return DPT_OK;
+    if (int rc = dpt_train_backward(&run, blob, tokens, ws + w.train, dpreds, ws + w.dblob, stream)) return rc;
+    return dpt_adamw_step(blob, ws + w.dblob, m, v, nblob, opt, stream);
+}
+
+// the checks of the fresh-task steps that precede the generator's own (dpt_fresh_batch)
+static int check_fresh_args(const char* who, const dpt_train_desc* d, const dpt_fresh_args* a, int32_t batch) {
+    DPT_REQUIRE(d && a, "%s: null desc / args", who);
+    DPT_REQUIRE(batch >= 1 && batch <= d->batch, "%s: batch=%d outside 1..desc.batch=%d", who, batch, d->batch);
+    DPT_REQUIRE(d->reserved == 0, "%s: desc flags must be 0 (got 0x%x)", who, d->reserved);
+    DPT_REQUIRE((int64_t)d->window == 1 + (int64_t)a->H, "%s: desc.window=%d != 1 + H=%d", who, d->window, a->H);
+    return check_action_dim(who, d->action_dim);
+}
+
 }  // namespace dpt
 
 using namespace dpt;
@@ -272,23 +310,10 @@ int dpt_train_step(const dpt_train_desc* d, const dpt_train_data* data, const in
     if (int rc = check_action_dim("train step", d->action_dim)) return rc;
     DPT_REQUIRE((int64_t)d->window == 1 + (int64_t)data->horizon, "train step: desc.window=%d != 1 + horizon=%d",
                 d->window, data->horizon);
-    StepWs w;
-    if (int rc = step_ws(d, w)) return rc;  // laid out for desc.batch; a smaller batch uses a prefix of each region
-    int64_t nblob = 0;
-    if (int rc = dpt_train_blob_numel(d, &nblob)) return rc;
-    dpt_train_desc run = *d;
-    run.batch = batch;
-    float *tokens = ws + w.tokens, *targets = ws + w.targets, *preds = ws + w.preds, *dpreds = ws + w.dpreds;
-    float* dblob = ws + w.dblob;
-    double* partial = reinterpret_cast<double*>(ws + w.partial);
-    DPT_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "train step: workspace not 16-byte aligned");
-    if (int rc = dpt_train_pack_batch(&run, data, index, perm, batch, tokens, targets, stream)) return rc;
-    if (int rc = dpt_train_forward(&run, blob, tokens, ws + w.train, preds, stream)) return rc;
-    if (int rc = dpt_train_ce_loss(preds, targets, batch, run.window, run.action_dim, dpreds, partial, loss_acc,
-                                   stream))
-        return rc;
-    if (int rc = dpt_train_backward(&run, blob, tokens, ws + w.train, dpreds, dblob, stream)) return rc;
-    return dpt_adamw_step(blob, dblob, m, v, nblob, opt, stream);
+    return step_chain("train step", d, batch, blob, blob, m, v, opt, ws, loss_acc, stream,
+                      [&](const dpt_train_desc& run, float* tokens, float* targets) {
+                          return dpt_train_pack_batch(&run, data, index, perm, batch, tokens, targets, stream);
+                      });
 }
 
 int dpt_train_eval_loss(const dpt_train_desc* d, const dpt_train_data* data, const int64_t* index,
@@ -299,17 +324,31 @@ int dpt_train_eval_loss(const dpt_train_desc* d, const dpt_train_data* data, con
     if (int rc = check_action_dim("train eval loss", d->action_dim)) return rc;
     DPT_REQUIRE((int64_t)d->window == 1 + (int64_t)data->horizon, "train eval loss: desc.window=%d != 1 + horizon=%d",
                 d->window, data->horizon);
-    StepWs w;
-    if (int rc = step_ws(d, w)) return rc;
-    DPT_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "train eval loss: workspace not 16-byte aligned");
-    dpt_train_desc run = *d;
-    run.batch = batch;
-    run.reserved = DPT_TRAIN_FORWARD_ONLY;  // every position's preds: never DPT_TRAIN_LAST_ONLY
-    float *tokens = ws + w.tokens, *targets = ws + w.targets, *preds = ws + w.preds;
-    double* partial = reinterpret_cast<double*>(ws + w.partial);
-    if (int rc = dpt_train_pack_batch(&run, data, index, perm, batch, tokens, targets, stream)) return rc;
-    if (int rc = dpt_train_forward(&run, blob, tokens, ws + w.train, preds, stream)) return rc;
-    return dpt_train_ce_loss(preds, targets, batch, run.window, run.action_dim, nullptr, partial, loss_acc, stream);
+    return step_chain("train eval loss", d, batch, blob, nullptr, nullptr, nullptr, nullptr, ws, loss_acc, stream,
+                      [&](const dpt_train_desc& run, float* tokens, float* targets) {
+                          return dpt_train_pack_batch(&run, data, index, perm, batch, tokens, targets, stream);
+                      });
+}
+
+int dpt_fresh_step(const dpt_train_desc* d, const dpt_fresh_args* a, int32_t batch, float* blob, float* m, float* v,
+                   const dpt_adamw_args* opt, float* ws, double* loss_acc, void* stream) {
+    if (int rc = check_fresh_args("fresh step", d, a, batch)) return rc;
+    DPT_REQUIRE(blob && m && v && opt && ws && loss_acc, "fresh step: null pointer");
+    DPT_REQUIRE(opt->step >= 1, "fresh step: step=%lld (the first step is 1)", (long long)opt->step);
+    return step_chain("fresh step", d, batch, blob, blob, m, v, opt, ws, loss_acc, stream,
+                      [&](const dpt_train_desc& run, float* tokens, float* targets) {
+                          return dpt_fresh_batch(&run, a, batch, tokens, targets, stream);
+                      });
+}
+
+int dpt_fresh_eval_loss(const dpt_train_desc* d, const dpt_fresh_args* a, int32_t batch, const float* blob, float* ws,
+                        double* loss_acc, void* stream) {
+    if (int rc = check_fresh_args("fresh eval loss", d, a, batch)) return rc;
+    DPT_REQUIRE(blob && ws && loss_acc, "fresh eval loss: null pointer");
+    return step_chain("fresh eval loss", d, batch, blob, nullptr, nullptr, nullptr, nullptr, ws, loss_acc, stream,
+                      [&](const dpt_train_desc& run, float* tokens, float* targets) {
+                          return dpt_fresh_batch(&run, a, batch, tokens, targets, stream);
+                      });
 }
 
 }  // extern "C"

@@ -361,6 +361,69 @@ def rollin_darkroom(goals, H, dim=10, perm=None, mode=0, states=None, actions=No
     return out
 
 
+# ----------------------------------------------------------------------------- fresh-task generator
+
+class FreshEnv:
+    """What the fresh-task generator (dpt_fresh_batch) draws its samples from: ``FreshEnv.bandit(A, H, var,
+    "uniform" | "bernoulli")`` or ``FreshEnv.darkroom(dim, H, goals, perms=None)`` with ``goals`` (G, 2) the
+    list the task's goal is drawn from (a held-out split: the train list or the test list) and ``perms``
+    (P, 5) an optional list of action permutations.  The lists are int32 device tensors, kept here."""
+
+    def __init__(self, kind, dim, H, var=0.0, bandit_type=BANDIT_GAUSSIAN, goals=None, perms=None):
+        self.kind, self.dim, self.H, self.var, self.type = int(kind), int(dim), int(H), float(var), int(bandit_type)
+        self.goals = self.perms = None
+        if kind == _lib.FRESH_DARKROOM:
+            self.goals = _dev(goals, torch.int32).reshape(-1, 2)
+            self.perms = None if perms is None else _dev(perms, torch.int32, self.goals.device).reshape(-1, 5)
+        self.state_dim, self.action_dim = (1, self.dim) if kind == _lib.FRESH_BANDIT else (2, 5)
+
+    @classmethod
+    def bandit(cls, A, H, var, bandit_type="uniform"):
+        code = {"uniform": BANDIT_GAUSSIAN, "bernoulli": BANDIT_BERNOULLI}.get(bandit_type, bandit_type)
+        return cls(_lib.FRESH_BANDIT, A, H, var, code)
+
+    @classmethod
+    def darkroom(cls, dim, H, goals, perms=None):
+        return cls(_lib.FRESH_DARKROOM, dim, H, goals=goals, perms=perms)
+
+    def args(self, seed, first_task, outs=None):
+        """dpt_fresh_args for the samples from ``first_task`` on; ``outs``: the optional outputs by name."""
+        o = outs or {}
+        return _lib.FreshArgs(
+            self.kind, self.type, self.dim, self.H, 0 if self.goals is None else int(self.goals.shape[0]),
+            0 if self.perms is None else int(self.perms.shape[0]), self.var, int(seed) & (2 ** 64 - 1),
+            int(first_task), *(None if t is None else t.data_ptr() for t in (
+                self.goals, self.perms, o.get("means"), o.get("probs"), o.get("goal"), o.get("perm"), o.get("query"),
+                o.get("opt_action"))))
+
+
+def fresh_batch(env, seed, first_task, n, outputs=True):
+    """The generator alone (dpt_fresh_batch): samples ``first_task`` .. ``first_task + n - 1`` of ``env`` (a
+    ``FreshEnv``) under the Philox key ``seed``, each a function of (seed, its global index) alone.  Returns a
+    dict of device tensors: ``tokens`` (n, 1 + H, 2 sd + A + 1) and ``targets`` (n, A) fp32 -- what the
+    training step packs from a dataset of these samples -- and, with ``outputs``, ``opt_action`` (n) int32 and
+    the task itself: ``means`` / ``probs`` (n, A) float64 for a bandit, ``goal`` (n, 2), ``perm`` (n, 5) and
+    ``query`` (n, 2) int32 for DarkRoom."""
+    dev, n = device(), int(n)
+    sd, A, T = env.state_dim, env.action_dim, 1 + env.H
+    out = dict(tokens=torch.empty((n, T, 2 * sd + A + 1), dtype=torch.float32, device=dev),
+               targets=torch.empty((n, A), dtype=torch.float32, device=dev))
+    if outputs:
+        out["opt_action"] = torch.empty(n, dtype=torch.int32, device=dev)
+        if env.kind == _lib.FRESH_BANDIT:
+            out.update(means=torch.empty((n, A), dtype=torch.float64, device=dev),
+                       probs=torch.empty((n, A), dtype=torch.float64, device=dev))
+        else:
+            out.update(goal=torch.empty((n, 2), dtype=torch.int32, device=dev),
+                       perm=torch.empty((n, 5), dtype=torch.int32, device=dev),
+                       query=torch.empty((n, 2), dtype=torch.int32, device=dev))
+    d = _lib.TrainDesc(1, E, sd, A, T, n, T, 0, 0.0, 0, 0)  # the generator reads state_dim, action_dim, batch, window
+    args = env.args(seed, first_task, out)
+    _lib.call("dpt_fresh_batch", ctypes.byref(d), ctypes.byref(args), n, _p(out["tokens"]), _p(out["targets"]),
+              _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- in-episode DarkRoom rollout
 
 def rollout_darkroom_episode(model, goals, K, dim, sample=True, perm=None, uniforms=None, seed=None, first_task=0,

@@ -30,6 +30,7 @@ STREAM_REWARD = 1
 STREAM_ROLLIN = 2
 STREAM_DROPOUT = 3  # training dropout masks (dpt_train_desc)
 STREAM_ENVACT = 4  # the env action drawn apart from the context action (dpt_rollout_bandit_generic_env)
+STREAM_TASK = 5  # the task draws of the fresh-task generator (dpt_fresh_batch)
 STREAM_POLICY = 16  # + arm index (baseline-policy draws)
 
 _c_void_p = ctypes.c_void_p
@@ -233,6 +234,26 @@ SIGNATURES["dpt_train_step"] = (_i32, [_train_desc_p, _train_data_p, _c_void_p, 
                                        _c_void_p])
 SIGNATURES["dpt_train_eval_loss"] = (_i32, [_train_desc_p, _train_data_p, _c_void_p, _c_void_p, _i32, _c_void_p,
                                             _c_void_p, _c_void_p, _c_void_p])
+
+
+FRESH_BANDIT = 0  # dpt_fresh_args.env
+FRESH_DARKROOM = 1
+
+
+class FreshArgs(ctypes.Structure):
+    """dpt_fresh_args: the fresh-task generator's samples first_task .. first_task + batch - 1."""
+    _fields_ = [("env", _i32), ("type", _i32), ("dim", _i32), ("H", _i32), ("n_goals", _i32), ("n_perms", _i32),
+                ("var", _f64), ("seed", _u64), ("first_task", _i64), ("goals", _c_void_p), ("perms", _c_void_p),
+                ("means_out", _c_void_p), ("probs_out", _c_void_p), ("goal_out", _c_void_p), ("perm_out", _c_void_p),
+                ("query_out", _c_void_p), ("opt_action_out", _c_void_p)]
+
+
+_fresh_args_p = ctypes.POINTER(FreshArgs)
+SIGNATURES["dpt_fresh_batch"] = (_i32, [_train_desc_p, _fresh_args_p, _i32, _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_fresh_step"] = (_i32, [_train_desc_p, _fresh_args_p, _i32, _c_void_p, _c_void_p, _c_void_p,
+                                       ctypes.POINTER(AdamWArgs), _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_fresh_eval_loss"] = (_i32, [_train_desc_p, _fresh_args_p, _i32, _c_void_p, _c_void_p, _c_void_p,
+                                            _c_void_p])
 
 
 INTERACTIVE_ACCUMULATE = 1  # dpt_interactive_args.flags: dblob += the chunk's gradient

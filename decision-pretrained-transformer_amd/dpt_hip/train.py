@@ -12,12 +12,15 @@ holding the forward's saved activations is a torch tensor kept on the autograd c
 image front end (dpt_image_front_forward / _backward: conv encoder, embed_transition, embed_ln) chained
 into the trunk through dpt_train_forward_embeds / dpt_train_backward_embeds.
 
-The five fused trainers keep everything on the device.  ``ModelState`` is one model's master blob with
+The fused trainers keep everything on the device.  ``ModelState`` is one model's master blob with
 AdamW's ``m`` / ``v`` (and a gradient blob); ``_TrainerCore`` holds the hyper-parameters, the step count
 and the loss accumulator(s).  Under it, ``_DatasetTrainer`` is the one-call step on a device-resident
 dataset: ``Trainer`` (train.py; dpt_train_step on a ``DeviceData``: batch packing, forward, summed
 cross-entropy, backward, AdamW) and ``ImageTrainer`` (train_miniworld.py --fused; dpt_image_train_step on
-a ``DeviceImageData``: the image front end and the trunk, two blobs).  ``_BanditTrainer`` is the on-policy
+a ``DeviceImageData``: the image front end and the trunk, two blobs).  ``FreshTrainer`` (train_fresh.py;
+dpt_fresh_step) is ``Trainer``'s step without a dataset: each batch is generated on the device from Philox
+(``dpt_hip.FreshEnv``), and ``fresh_dataset`` materialises such samples in the ``DeviceData`` layout.
+``_BanditTrainer`` is the on-policy
 bandit episode, a gradient call per chunk of envs and then dpt_adamw_step per model:
 ``InteractiveTrainer`` (train_interactive.py; dpt_interactive_grad: the y-cache rollout straight from the
 master blob, the window packed from its records, forward, last-position cross-entropy, backward) and
@@ -553,6 +556,91 @@ class Trainer(_DatasetTrainer):
         super().__init__(model, lr, weight_decay, betas, eps)
         self.state = ModelState(pack_params(param_list(model), self.loss.device))
         self._states = (self.state,)
+
+    def sync_to_model(self):
+        """Unpack the master blob into the module's parameters."""
+        return _sync(self.state, self.model)
+
+
+def fresh_dataset(first_task, n, env, seed):
+    """Samples ``first_task`` .. ``first_task + n - 1`` of the fresh-task generator (``dpt_hip.fresh_batch``)
+    materialised in the ``DeviceData`` / dpt_train_data layout: a dict of contiguous fp32 device tensors
+    (query_states, context_states, context_actions, context_next_states, context_rewards,
+    optimal_actions).  ``Trainer.step`` on it with index ``arange`` consumes what ``FreshTrainer.step``
+    generates in place; ``{k: v.cpu() ...}`` dumps a dataset."""
+    from . import fresh_batch
+    o = fresh_batch(env, seed, first_task, n, outputs=False)
+    tok, sd, A = o["tokens"], env.state_dim, env.action_dim
+    ctx = tok[:, 1:]
+    return {"query_states": tok[:, 0, :sd].contiguous(), "context_states": ctx[:, :, :sd].contiguous(),
+            "context_actions": ctx[:, :, sd:sd + A].contiguous(),
+            "context_next_states": ctx[:, :, sd + A:2 * sd + A].contiguous(),
+            "context_rewards": ctx[:, :, 2 * sd + A].contiguous(), "optimal_actions": o["targets"]}
+
+
+class FreshTrainer(_TrainerCore):
+    """The pretraining step on fresh tasks (train_fresh.py; dpt_fresh_step): no dataset -- each step
+    generates its batch on the device (``dpt_hip.FreshEnv``: the task, the behaviour policy, the rollin,
+    the query and the label, all from Philox(``seed``) and the sample's global index), then forward, summed
+    cross-entropy, backward and AdamW, the launches of ``Trainer.step`` after its pack.  ``step`` takes the
+    next ``batch`` samples from ``first_task`` on, so a run sees every task once whatever its batch sizes."""
+    blob, m, v = _of("state", "blob"), _of("state", "m"), _of("state", "v")
+
+    def __init__(self, model, env, lr, weight_decay=1e-4, seed=0, first_task=0, betas=(0.9, 0.999), eps=1e-8):
+        super().__init__(lr, weight_decay, betas, eps)
+        if (env.state_dim, env.action_dim, env.H) != (model.state_dim, model.action_dim, model.horizon):
+            raise ValueError(f"env (sd {env.state_dim}, A {env.action_dim}, H {env.H}) does not match the model "
+                             f"(sd {model.state_dim}, A {model.action_dim}, H {model.horizon})")
+        self.model, self.env, self.seed, self.first_task = model, env, int(seed), int(first_task)
+        self.state = ModelState(pack_params(param_list(model), self.loss.device))
+        self._ws_batch = 0  # the workspace grows to the largest batch seen
+
+    def _desc(self, batch, dropout_seed):
+        m = self.model
+        p = float(m.dropout) if m.dropout > 0 else 0.0
+        if p > 0 and dropout_seed is None:  # fresh masks per call; the test loss runs in training mode too
+            from models.net import _dropout_seed
+            dropout_seed = _dropout_seed()
+        cap = max(batch, self._ws_batch)
+        d = desc(m.n_layer, m.n_embd, m.state_dim, m.action_dim, m.n_positions, cap, 1 + self.env.H, dropout=p,
+                 seed=(int(dropout_seed) & (2 ** 64 - 1)) if p > 0 else 0)
+        if self._ws is None or cap > self._ws_batch:
+            self._ws = torch.empty(_numel("dpt_train_step_workspace_numel", d), dtype=torch.float32,
+                                   device=self.loss.device)
+            self._ws_batch = cap
+        return d
+
+    def step(self, batch=64, dropout_seed=None):
+        """One training step on the next ``batch`` fresh samples; adds their summed loss to the accumulator."""
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("empty batch")
+        d = self._desc(batch, dropout_seed)
+        args = self.env.args(self.seed, self.first_task)
+        self.steps += 1
+        try:
+            _lib.call("dpt_fresh_step", ctypes.byref(d), ctypes.byref(args), batch, *self.state.ptrs(),
+                      ctypes.byref(self._adamw_args()), _p(self._ws), _p(self.loss), _stream())
+        except Exception:
+            self.steps -= 1  # rejected on the host before any launch
+            raise
+        self.first_task += batch
+
+    def eval_loss(self, first_task, n, seed=None, env=None, batch=64, dropout_seed=None):
+        """The test loss on samples ``first_task`` .. ``first_task + n - 1`` of ``env`` (default: the training
+        env) under the key ``seed`` (default: the training key), ``batch`` at a time: forward only, the model's
+        dropout active; adds the summed loss to the accumulator.  Nothing is stored: the same arguments
+        regenerate the same samples."""
+        env = env or self.env
+        if (env.state_dim, env.action_dim, env.H) != (self.env.state_dim, self.env.action_dim, self.env.H):
+            raise ValueError("eval_loss: the env's shapes differ from the training env's")
+        seed = self.seed if seed is None else int(seed)
+        for lo in range(0, int(n), int(batch)):
+            b = min(int(batch), int(n) - lo)
+            d = self._desc(b, dropout_seed)
+            args = env.args(seed, int(first_task) + lo)
+            _lib.call("dpt_fresh_eval_loss", ctypes.byref(d), ctypes.byref(args), b, _p(self.state.blob),
+                      _p(self._ws), _p(self.loss), _stream())
 
     def sync_to_model(self):
         """Unpack the master blob into the module's parameters."""

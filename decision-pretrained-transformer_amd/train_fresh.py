@@ -1,0 +1,132 @@
+"""Pretraining on fresh tasks: train.py without collect_data.py, a dataset file or a resident dataset.
+
+Every batch is generated on the device where the training step consumes it
+(dpt_hip.train.FreshTrainer -> dpt_fresh_step): the task, the behaviour policy, the rollin with its
+reward noise, the query state and the optimal-action label are Philox draws keyed by ``--seed`` and the
+sample's global index, so each step sees tasks no earlier step saw and nothing is stored.
+
+Flags: train.py's, plus ``--batch`` (default 64).  An epoch is ``int(0.8 * envs)`` fresh training samples;
+the test loss is taken over ``envs - int(0.8 * envs)`` samples regenerated every epoch from a fixed key
+distinct from the training key (``darkroom_heldout``: drawn from the 20 % of goals collect_data.py holds
+out, the training samples from the other 80 %; any other ``darkroom*`` name: every goal for both).  The log
+file, log lines, loss plot, checkpoint schedule and checkpoint names are train.py's, so eval.py with the same
+flags loads the result -- and a train.py checkpoint with equal flags is overwritten.  ``--hists``,
+``--samples`` and ``--shuffle`` only name the file: fresh tasks leave nothing to repeat, and the rollin
+steps are i.i.d., so permuting them changes nothing in law.
+"""
+import argparse
+import hashlib
+import os
+import time
+
+import numpy as np
+import torch
+
+import common_args
+from dpt_hip import FreshEnv
+from dpt_hip.train import FreshTrainer
+from models.net import Transformer
+from train_common import LossLog, set_seeds
+from utils import build_bandit_model_filename, build_darkroom_model_filename
+
+device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+
+
+def generator_key(seed, role):
+    """The 64-bit Philox key of the ``role`` ('train' / 'test') samples of a run seeded ``seed``."""
+    return int.from_bytes(hashlib.sha256(f"train_fresh/{role}/{seed}".encode()).digest()[:8], "little")
+
+
+def darkroom_goals(env, dim):
+    """(train goals, test goals) as (G, 2) arrays: collect_data.py's split for darkroom_heldout (the
+    shuffled grid, the first 80 % for training), else the whole grid for both."""
+    goals = np.array([[(j, i) for i in range(dim)] for j in range(dim)]).reshape(-1, 2)
+    if env != "darkroom_heldout":
+        return goals, goals
+    np.random.RandomState(seed=0).shuffle(goals)
+    split = int(.8 * len(goals))
+    return goals[:split], goals[split:]
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser()
+    common_args.add_dataset_args(parser)
+    common_args.add_model_args(parser)
+    common_args.add_train_args(parser)
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--batch", type=int, default=64)
+    args = vars(parser.parse_args(argv))
+    print("Args: ", args)
+
+    env, n_envs, horizon, dim = args["env"], args["envs"], args["H"], args["dim"]
+    lr, shuffle, seed, batch = args["lr"], args["shuffle"], args["seed"], args["batch"]
+    var, cov = args["var"], args["cov"]
+    if env == "linear_bandit":
+        raise NotImplementedError("linear_bandit: its rollin is an adaptive Thompson run (a chain through "
+                                  "dpt_rollout_policy), not i.i.d. draws; use collect_data.py and train.py")
+    if batch < 1:
+        raise ValueError(f"--batch {batch}")
+
+    os.makedirs("figs/loss", exist_ok=True)
+    os.makedirs("trained_models", exist_ok=True)
+    set_seeds(0 if seed == -1 else seed)
+
+    model_config = {"shuffle": shuffle, "lr": lr, "dropout": args["dropout"], "n_embd": args["embd"],
+                    "n_layer": args["layer"], "n_head": args["head"], "n_envs": n_envs, "n_hists": args["hists"],
+                    "n_samples": args["samples"], "horizon": horizon, "dim": dim, "seed": seed}
+    if env in ("bandit", "bandit_thompson"):
+        state_dim, action_dim = 1, dim
+        model_config.update({"var": var, "cov": cov})
+        filename = build_bandit_model_filename(env, model_config)
+        train_env = test_env = FreshEnv.bandit(dim, horizon, var, "uniform" if env == "bandit" else "bernoulli")
+    elif env.startswith("darkroom"):
+        state_dim, action_dim = 2, 5
+        filename = build_darkroom_model_filename(env, model_config)
+        train_goals, test_goals = darkroom_goals(env, dim)
+        train_env = FreshEnv.darkroom(dim, horizon, train_goals)
+        test_env = FreshEnv.darkroom(dim, horizon, test_goals)
+    else:
+        raise NotImplementedError(f"{env} (miniworld trains with train_miniworld.py)")
+
+    config = {"horizon": horizon, "state_dim": state_dim, "action_dim": action_dim, "n_layer": args["layer"],
+              "n_embd": args["embd"], "n_head": args["head"], "shuffle": shuffle, "dropout": args["dropout"],
+              "test": False, "store_gpu": True}
+    model = Transformer(config).to(device)
+
+    printw = LossLog(filename)
+
+    n_train = int(.8 * n_envs)
+    n_test = n_envs - n_train
+    train_key, test_key = generator_key(seed, "train"), generator_key(seed, "test")
+    trainer = FreshTrainer(model, train_env, lr=lr, weight_decay=1e-4, seed=train_key)
+
+    test_loss, train_loss = [], []
+    printw("Num train batches: " + str(-(-n_train // batch)))
+    printw("Num test batches: " + str(-(-n_test // batch)))
+
+    for epoch in range(args["num_epochs"]):
+        printw(f"Epoch: {epoch + 1}")
+        start_time = time.time()
+        trainer.eval_loss(0, n_test, seed=test_key, env=test_env, batch=batch)
+        test_loss.append(trainer.read_loss() / horizon / max(n_test, 1))
+        printw(f"\tTest loss: {test_loss[-1]}")
+        printw(f"\tEval time: {time.time() - start_time}")
+
+        start_time = time.time()
+        for lo in range(0, n_train, batch):
+            trainer.step(min(batch, n_train - lo))
+        train_loss.append(trainer.read_loss() / horizon / max(n_train, 1))
+        printw(f"\tTrain loss: {train_loss[-1]}")
+        printw(f"\tTrain time: {time.time() - start_time}")
+
+        if (epoch + 1) % 50 == 0:
+            torch.save(trainer.sync_to_model().state_dict(), f"trained_models/{filename}_epoch{epoch + 1}.pt")
+
+        printw.report(epoch, test_loss, train_loss)
+
+    torch.save(trainer.sync_to_model().state_dict(), f"trained_models/{filename}.pt")
+    print("Done.")
+
+
+if __name__ == "__main__":
+    main()

@@ -63,7 +63,8 @@ extern "C" {
  * evaluation (dpt_recommend_curve, dpt_empirical_recommend, dpt_exploit_eval_workspace_numel,
  * dpt_exploit_eval); the interactive DarkRoom training step (dpt_mdp_pack, dpt_darkroom_act_step,
  * dpt_interactive_mdp_workspace_numel, dpt_interactive_mdp_grad); the in-episode DarkRoom rollout in one
- * launch (dpt_rollout_darkroom_episode) */
+ * launch (dpt_rollout_darkroom_episode); the fresh-task generator and its training step (DPT_STREAM_TASK,
+ * dpt_fresh_args, dpt_fresh_batch, dpt_fresh_step, dpt_fresh_eval_loss) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -89,6 +90,12 @@ extern "C" {
 #define DPT_STREAM_ROLLIN 2
 #define DPT_STREAM_DROPOUT 3 /* training dropout masks: counter (site, element / 4), word element % 4 */
 #define DPT_STREAM_ENVACT 4  /* the env action of dpt_rollout_bandit_generic_env when it is drawn apart from the context action */
+/* the task draws of the fresh-task generator (dpt_fresh_batch), per task at counters:
+ *   bandit, A arms:  k in [0, A): means[k] = the 53-bit uniform;  A + k: e_k = -log(1 - uniform), the
+ *                    Gamma(1) variates of Dirichlet(1_A);  2 A: word 0 -> index into the 11-point cov
+ *                    grid, word 1 -> the point-mass arm (multiply-shift, as every integer draw)
+ *   DarkRoom:        0: word 0 -> index into the goal list, word 1 -> index into the permutation list */
+#define DPT_STREAM_TASK 5
 #define DPT_STREAM_POLICY 16/* + arm index: baseline-policy draws (Thompson posterior samples) */
 
 int dpt_abi_version(void);
@@ -554,6 +561,67 @@ int dpt_train_step(const dpt_train_desc* desc_host, const dpt_train_data* data_h
 int dpt_train_eval_loss(const dpt_train_desc* desc_host, const dpt_train_data* data_host, const int64_t* index,
                         const int64_t* perm, int32_t batch, const float* blob, float* workspace,
                         double* loss_acc, void* stream);
+
+/* ------------------------------------------------------------------ fresh-task training step
+ * The pretraining step on tasks nobody stored: the batch dpt_train_pack_batch would gather from a
+ * dataset is generated where it is consumed.  Sample b is global task first_task + b, and everything
+ * about it -- the task, the behaviour policy, the H i.i.d. rollin steps with their reward noise, the
+ * query state and the optimal-action label -- is a function of (seed, first_task + b) alone: not of
+ * `batch`, of how a run is cut into steps, or of the device.  One workgroup per sample, one launch.
+ *
+ * Bandit (env DPT_FRESH_BANDIT, desc.state_dim 1, dim = desc.action_dim = A <= 32; envs/bandit_env.py:10-18,
+ * collect_data.py:30-36): means[k] ~ U[0, 1) (Beta(1, 1): both reward types), the behaviour policy
+ * probs = (1 - cov) p + cov e_rand with p = e / sum(e) ~ Dirichlet(1_A) in fp64, cov = index / 10 from
+ * the 11-point grid and rand uniform over the arms (draws: DPT_STREAM_TASK above).  Row 1 + h of the
+ * sample = [1 | onehot(arm_h) | 1 | float(r_h)] with arm_h and r_h the values dpt_rollin_bandit gives for
+ * (means, probs, seed, first_task + b) at step h (DPT_STREAM_ROLLIN / DPT_STREAM_REWARD at counter h);
+ * row 0 = [1 | 0 ...]; target = the one-hot of the first argmax of means.
+ * DarkRoom (env DPT_FRESH_DARKROOM, desc.state_dim 2, desc.action_dim 5, dim <= 255;
+ * collect_data.py:189-218 with rollin_type 'uniform'): the goal is an entry of the caller's list goals
+ * (n_goals, 2) int32 -- a held-out split is respected by passing the train or the test list -- and the
+ * action permutation an entry of perms (n_perms, 5) int32 when perms is given.  Row 1 + h =
+ * [s | onehot(a) | s' | r], row 0 = [query | 0 ...] and the target = the one-hot of the expert action at
+ * the query: the values dpt_rollin_darkroom (mode 0) gives for (goal, perm, seed, first_task + b).
+ * Optional outputs (NULL: not written): means_out / probs_out (batch, A) fp64 (bandit); goal_out
+ * (batch, 2), perm_out (batch, 5; identity without a list), query_out (batch, 2) (DarkRoom);
+ * opt_action_out (batch) int32: the label's index (both).                                    */
+#define DPT_FRESH_BANDIT 0
+#define DPT_FRESH_DARKROOM 1
+typedef struct dpt_fresh_args {
+    int32_t env;            /* DPT_FRESH_BANDIT / DPT_FRESH_DARKROOM                            */
+    int32_t type;           /* bandit: DPT_BANDIT_GAUSSIAN / DPT_BANDIT_BERNOULLI               */
+    int32_t dim;            /* bandit: arms; DarkRoom: side of the room                         */
+    int32_t H;              /* rollin steps: desc.window = 1 + H                                */
+    int32_t n_goals;        /* DarkRoom: entries of goals, >= 1                                 */
+    int32_t n_perms;        /* DarkRoom: entries of perms (0 with perms NULL)                   */
+    double var;             /* bandit: reward noise std                                         */
+    uint64_t seed;          /* Philox key                                                       */
+    int64_t first_task;     /* global index of sample 0                                         */
+    const int32_t* goals;   /* (n_goals, 2) or NULL (bandit)                                    */
+    const int32_t* perms;   /* (n_perms, 5) or NULL                                             */
+    double* means_out;
+    double* probs_out;
+    int32_t* goal_out;
+    int32_t* perm_out;
+    int32_t* query_out;
+    int32_t* opt_action_out;
+} dpt_fresh_args;
+/* the generator alone: tokens (batch, 1 + H, 2 sd + A + 1) and targets (batch, A) fp32, what
+ * dpt_train_pack_batch writes for a dataset holding these samples.  Host-side checks (null pointers,
+ * batch outside 1..desc.batch, desc.window != 1 + H, H < 0, the desc's state_dim / action_dim against the
+ * env, n_goals < 1, dim < 1; action_dim > 32 and dim > 255 -> DPT_EUNSUPPORTED) fail before the launch. */
+int dpt_fresh_batch(const dpt_train_desc* desc_host, const dpt_fresh_args* args_host, int32_t batch, float* tokens,
+                    float* targets, void* stream);
+/* dpt_train_step with the generator in place of the pack: generator -> dpt_train_forward ->
+ * cross-entropy -> dpt_train_backward -> AdamW, the same launches after the batch with the same
+ * arguments, on the dpt_train_step_workspace_numel workspace.  desc flags 0; dropout through
+ * desc.dropout / desc.dropout_seed. */
+int dpt_fresh_step(const dpt_train_desc* desc_host, const dpt_fresh_args* args_host, int32_t batch, float* blob,
+                   float* m, float* v, const dpt_adamw_args* adamw_host, float* workspace, double* loss_acc,
+                   void* stream);
+/* dpt_train_eval_loss on generated samples: forward only, desc.dropout active, the loss alone. */
+int dpt_fresh_eval_loss(const dpt_train_desc* desc_host, const dpt_fresh_args* args_host, int32_t batch,
+                        const float* blob, float* workspace, double* loss_acc, void* stream);
 
 /* ------------------------------------------------------------------ interactive training step
  * One episode of train_interactive.py:92-143 (the on-policy variant: sample fresh bandits, roll the
