@@ -456,6 +456,8 @@ int launch_rollin_darkroom(const int32_t*, const int32_t*, int, int, int, int, c
                            uint64_t, int64_t, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*, int32_t*,
                            hipStream_t);
 int set_select_fast(int);
+// dpt_fresh_linear.hip
+int fresh_linear_check(const char* who, const dpt_train_desc*, const dpt_fresh_linear_args*, int32_t batch);
 // dpt_policies.hip
 int launch_rollout_policy(const dpt_policy_rollout_args&, hipStream_t);
 int set_policy_wave(int on);

@@ -10,23 +10,16 @@
 // store consecutive words.  The kernels read nothing but the goal / permutation lists, write the bytes the
 // pack wrote (about 1 MB at batch 64, window 501, 5 arms) and allocate nothing.
 #include "dpt_common.h"
+#include "dpt_fresh.h"
 #include "dpt_rollin.h"
 
 namespace dpt {
 
-constexpr int kFreshThreads = 256;
 constexpr int kFreshMaxDim = 255;  // a DarkRoom coordinate is recorded in one byte
 
-// the rows 1 + h0 .. 1 + h0 + rows - 1 of one sample, F floats each, element (row, f) = val(row, f)
-template <class Val>
-__device__ inline void fresh_store_rows(float* __restrict__ dst, int rows, int F, Val val) {
-    const int n = rows * F;
-    for (int e = threadIdx.x; e < n; e += kFreshThreads) {
-        const int row = e / F;
-        dst[e] = val(row, e - row * F);
-    }
-}
-
+// The task's means at counters [0, A), then the behaviour policy from counter A on and the rows: the shared
+// pieces of dpt_fresh.h (fresh_bandit_policy; fresh_bandit_rows, which runs rollin_bandit_arm() and
+// rollin_bandit_reward() of dpt_rollin.h once per step), the same code the linear bandit's 'uniform' rollin runs.
 __global__ __launch_bounds__(kFreshThreads) void fresh_bandit_kernel(int A, int H, int type, double var,
                                                                      uint64_t seed, int64_t first_task,
                                                                      float* __restrict__ tokens,
@@ -41,21 +34,11 @@ __global__ __launch_bounds__(kFreshThreads) void fresh_bandit_kernel(int A, int 
     const int b = blockIdx.x, tid = threadIdx.x;
     const int64_t task = first_task + b;
     const int F = A + 3;  // [1 | onehot(arm) | 1 | r]
+    if (tid < A) s_means[tid] = philox_uniform(seed, tid, task, DPT_STREAM_TASK);
+    fresh_bandit_policy(A, seed, task, A, s_e, s_probs);
     if (tid < A) {
-        s_means[tid] = philox_uniform(seed, tid, task, DPT_STREAM_TASK);
-        s_e[tid] = -log(1.0 - philox_uniform(seed, A + tid, task, DPT_STREAM_TASK));  // Gamma(1) = Exp(1)
-    }
-    __syncthreads();
-    if (tid < A) {
-        double total = 0.0;  // every lane sums in index order: one value
-        for (int k = 0; k < A; ++k) total += s_e[k];
-        // the grid point index / 10 is the correctly rounded decimal: the double that 0.1, 0.2, ... name
-        const double cov = (double)philox_randint(seed, 2 * A, task, DPT_STREAM_TASK, 0, 11) / 10.0;
-        const int rand_index = philox_randint(seed, 2 * A, task, DPT_STREAM_TASK, 1, A);
-        const double p = (1.0 - cov) * (s_e[tid] / total) + cov * (tid == rand_index ? 1.0 : 0.0);
-        s_probs[tid] = p;
         if (means_out) means_out[(int64_t)b * A + tid] = s_means[tid];
-        if (probs_out) probs_out[(int64_t)b * A + tid] = p;
+        if (probs_out) probs_out[(int64_t)b * A + tid] = s_probs[tid];
     }
     if (tid == 0) {
         int best = 0;
@@ -68,20 +51,7 @@ __global__ __launch_bounds__(kFreshThreads) void fresh_bandit_kernel(int A, int 
     float* tok = tokens + (int64_t)b * (1 + H) * F;
     if (tid < F) tok[tid] = tid == 0 ? 1.f : 0.f;  // the query token [1 | 0 ...]
     if (tid < A) targets[(int64_t)b * A + tid] = tid == s_best ? 1.f : 0.f;
-    for (int h0 = 0; h0 < H; h0 += kFreshThreads) {
-        const int h = h0 + tid;
-        if (h < H) {
-            const double u = philox_uniform(seed, h, task, DPT_STREAM_ROLLIN);
-            const int a = rollin_bandit_arm(s_probs, A, u);
-            s_arm[tid] = a;
-            s_r[tid] = (float)rollin_bandit_reward(type, s_means[a], var, false, 0.0, seed, h, task);
-        }
-        __syncthreads();
-        fresh_store_rows(tok + (int64_t)(1 + h0) * F, min(kFreshThreads, H - h0), F, [&](int row, int f) {
-            return f == 0 || f == A + 1 ? 1.f : f == A + 2 ? s_r[row] : (s_arm[row] == f - 1 ? 1.f : 0.f);
-        });
-        __syncthreads();
-    }
+    fresh_bandit_rows(A, H, type, var, seed, task, s_means, s_probs, s_arm, s_r, tok);
 }
 
 __global__ __launch_bounds__(kFreshThreads) void fresh_darkroom_kernel(const int32_t* __restrict__ goals,

@@ -1,8 +1,8 @@
 // The training step around dpt_train_forward / dpt_train_backward (include/dpt_hip.h, "training
 // step"): batch packing from a device-resident dataset, the summed cross-entropy of train.py:295-301
 // with its gradient, AdamW over the whole packed blob, and the entry points that chain them on one
-// stream without a host synchronisation; the fresh-task steps are the same chain with the generator of
-// dpt_fresh.hip in place of the pack.  Nothing here allocates: every buffer is the caller's.
+// stream without a host synchronisation; the fresh-task steps are the same chain with a generator
+// (dpt_fresh.hip, dpt_fresh_linear.hip) in place of the pack.  Nothing here allocates: every buffer is the caller's.
 //
 // Arithmetic: the cross-entropy and the AdamW update are evaluated in fp64 per element from the
 // fp32 inputs and rounded once on the store (both kernels are bound by their loads and stores, the
@@ -232,6 +232,14 @@ static int check_fresh_args(const char* who, const dpt_train_desc* d, const dpt_
     return check_action_dim(who, d->action_dim);
 }
 
+// the same for the linear bandit: every check of its generator (dpt_fresh_linear.hip), then the desc flags
+static int check_fresh_linear_args(const char* who, const dpt_train_desc* d, const dpt_fresh_linear_args* a,
+                                   int32_t batch) {
+    if (int rc = fresh_linear_check(who, d, a, batch)) return rc;
+    DPT_REQUIRE(d->reserved == 0, "%s: desc flags must be 0 (got 0x%x)", who, d->reserved);
+    return DPT_OK;
+}
+
 }  // namespace dpt
 
 using namespace dpt;
@@ -348,6 +356,27 @@ int dpt_fresh_eval_loss(const dpt_train_desc* d, const dpt_fresh_args* a, int32_
     return step_chain("fresh eval loss", d, batch, blob, nullptr, nullptr, nullptr, nullptr, ws, loss_acc, stream,
                       [&](const dpt_train_desc& run, float* tokens, float* targets) {
                           return dpt_fresh_batch(&run, a, batch, tokens, targets, stream);
+                      });
+}
+
+int dpt_fresh_linear_step(const dpt_train_desc* d, const dpt_fresh_linear_args* a, int32_t batch, float* blob,
+                          float* m, float* v, const dpt_adamw_args* opt, float* ws, double* loss_acc, void* stream) {
+    if (int rc = check_fresh_linear_args("fresh linear step", d, a, batch)) return rc;
+    DPT_REQUIRE(blob && m && v && opt && ws && loss_acc, "fresh linear step: null pointer");
+    DPT_REQUIRE(opt->step >= 1, "fresh linear step: step=%lld (the first step is 1)", (long long)opt->step);
+    return step_chain("fresh linear step", d, batch, blob, blob, m, v, opt, ws, loss_acc, stream,
+                      [&](const dpt_train_desc& run, float* tokens, float* targets) {
+                          return dpt_fresh_linear_batch(&run, a, batch, tokens, targets, stream);
+                      });
+}
+
+int dpt_fresh_linear_eval_loss(const dpt_train_desc* d, const dpt_fresh_linear_args* a, int32_t batch,
+                               const float* blob, float* ws, double* loss_acc, void* stream) {
+    if (int rc = check_fresh_linear_args("fresh linear eval loss", d, a, batch)) return rc;
+    DPT_REQUIRE(blob && ws && loss_acc, "fresh linear eval loss: null pointer");
+    return step_chain("fresh linear eval loss", d, batch, blob, nullptr, nullptr, nullptr, nullptr, ws, loss_acc,
+                      stream, [&](const dpt_train_desc& run, float* tokens, float* targets) {
+                          return dpt_fresh_linear_batch(&run, a, batch, tokens, targets, stream);
                       });
 }
 

@@ -364,18 +364,31 @@ def rollin_darkroom(goals, H, dim=10, perm=None, mode=0, states=None, actions=No
 # ----------------------------------------------------------------------------- fresh-task generator
 
 class FreshEnv:
-    """What the fresh-task generator (dpt_fresh_batch) draws its samples from: ``FreshEnv.bandit(A, H, var,
-    "uniform" | "bernoulli")`` or ``FreshEnv.darkroom(dim, H, goals, perms=None)`` with ``goals`` (G, 2) the
-    list the task's goal is drawn from (a held-out split: the train list or the test list) and ``perms``
-    (P, 5) an optional list of action permutations.  The lists are int32 device tensors, kept here."""
+    """What the fresh-task generators (dpt_fresh_batch, dpt_fresh_linear_batch) draw their samples from:
+    ``FreshEnv.bandit(A, H, var, "uniform" | "bernoulli")``, ``FreshEnv.darkroom(dim, H, goals, perms=None)``
+    with ``goals`` (G, 2) the list the task's goal is drawn from (a held-out split: the train list or the test
+    list) and ``perms`` (P, 5) an optional list of action permutations, or ``FreshEnv.linear_bandit(arms, H,
+    var, "thompson" | "uniform")`` with ``arms`` (A, d) the arm features.  The lists are int32 and the arms
+    float64 device tensors, kept here.  ``kind`` is FRESH_BANDIT, FRESH_DARKROOM or ``FreshEnv.LINEAR``, which
+    has entry points and an args struct of its own (``calls``, ``args``)."""
+    LINEAR = 2  # not a dpt_fresh_args.env: the linear bandit's generator is dpt_fresh_linear_batch
 
-    def __init__(self, kind, dim, H, var=0.0, bandit_type=BANDIT_GAUSSIAN, goals=None, perms=None):
+    def __init__(self, kind, dim, H, var=0.0, bandit_type=BANDIT_GAUSSIAN, goals=None, perms=None, arms=None,
+                 rollin=_lib.FRESH_LINEAR_THOMPSON):
         self.kind, self.dim, self.H, self.var, self.type = int(kind), int(dim), int(H), float(var), int(bandit_type)
-        self.goals = self.perms = None
+        self.goals = self.perms = self.arms = None
+        self.rollin = int(rollin)
         if kind == _lib.FRESH_DARKROOM:
             self.goals = _dev(goals, torch.int32).reshape(-1, 2)
             self.perms = None if perms is None else _dev(perms, torch.int32, self.goals.device).reshape(-1, 5)
-        self.state_dim, self.action_dim = (1, self.dim) if kind == _lib.FRESH_BANDIT else (2, 5)
+        if kind == self.LINEAR:
+            self.arms = _dev(arms, torch.float64)
+            if self.arms.dim() != 2 or self.arms.shape[0] != self.dim:
+                raise ValueError(f"arms {tuple(self.arms.shape)}: expected (A, d)")
+            self.lin_d = int(self.arms.shape[1])
+        self.state_dim, self.action_dim = (2, 5) if kind == _lib.FRESH_DARKROOM else (1, self.dim)
+        stem = "dpt_fresh_linear_" if kind == self.LINEAR else "dpt_fresh_"
+        self.calls = {k: stem + k for k in ("batch", "step", "eval_loss")}  # the C entry point of each use
 
     @classmethod
     def bandit(cls, A, H, var, bandit_type="uniform"):
@@ -386,24 +399,42 @@ class FreshEnv:
     def darkroom(cls, dim, H, goals, perms=None):
         return cls(_lib.FRESH_DARKROOM, dim, H, goals=goals, perms=perms)
 
+    @classmethod
+    def linear_bandit(cls, arms, H, var, rollin="thompson"):
+        """``arms`` (A, d): collect_data.py's are ``RandomState(1234).normal(size=(A, d)) / sqrt(d)``.  ``rollin``:
+        "thompson", the adaptive run of rollin_linear_bandit_vec (posterior prior 0 / 1, std ``var`` > 0), or
+        "uniform", the bandit's i.i.d. behaviour policy (collect_data.py's data_type 'uniform')."""
+        codes = {"thompson": _lib.FRESH_LINEAR_THOMPSON, "uniform": _lib.FRESH_LINEAR_UNIFORM}
+        if rollin not in codes:
+            raise ValueError(f"rollin {rollin!r}: 'thompson' or 'uniform'")
+        arms = arms if isinstance(arms, torch.Tensor) else np.asarray(arms, np.float64)
+        return cls(cls.LINEAR, arms.shape[0], H, var, arms=arms, rollin=codes[rollin])
+
     def args(self, seed, first_task, outs=None):
-        """dpt_fresh_args for the samples from ``first_task`` on; ``outs``: the optional outputs by name."""
+        """dpt_fresh_args (the linear bandit: dpt_fresh_linear_args) for the samples from ``first_task`` on;
+        ``outs``: the optional outputs by name."""
         o = outs or {}
+        ptr = lambda *ts: (None if t is None else t.data_ptr() for t in ts)  # noqa: E731
+        if self.kind == self.LINEAR:
+            return _lib.FreshLinearArgs(self.rollin, self.dim, self.lin_d, self.H, self.var,
+                                        int(seed) & (2 ** 64 - 1), int(first_task),
+                                        *ptr(self.arms, o.get("theta"), o.get("means"), o.get("probs"),
+                                             o.get("opt_action")))
         return _lib.FreshArgs(
             self.kind, self.type, self.dim, self.H, 0 if self.goals is None else int(self.goals.shape[0]),
             0 if self.perms is None else int(self.perms.shape[0]), self.var, int(seed) & (2 ** 64 - 1),
-            int(first_task), *(None if t is None else t.data_ptr() for t in (
-                self.goals, self.perms, o.get("means"), o.get("probs"), o.get("goal"), o.get("perm"), o.get("query"),
-                o.get("opt_action"))))
+            int(first_task), *ptr(self.goals, self.perms, o.get("means"), o.get("probs"), o.get("goal"),
+                                  o.get("perm"), o.get("query"), o.get("opt_action")))
 
 
 def fresh_batch(env, seed, first_task, n, outputs=True):
-    """The generator alone (dpt_fresh_batch): samples ``first_task`` .. ``first_task + n - 1`` of ``env`` (a
-    ``FreshEnv``) under the Philox key ``seed``, each a function of (seed, its global index) alone.  Returns a
-    dict of device tensors: ``tokens`` (n, 1 + H, 2 sd + A + 1) and ``targets`` (n, A) fp32 -- what the
-    training step packs from a dataset of these samples -- and, with ``outputs``, ``opt_action`` (n) int32 and
-    the task itself: ``means`` / ``probs`` (n, A) float64 for a bandit, ``goal`` (n, 2), ``perm`` (n, 5) and
-    ``query`` (n, 2) int32 for DarkRoom."""
+    """The generator alone (dpt_fresh_batch / dpt_fresh_linear_batch): samples ``first_task`` ..
+    ``first_task + n - 1`` of ``env`` (a ``FreshEnv``) under the Philox key ``seed``, each a function of (seed,
+    its global index) alone.  Returns a dict of device tensors: ``tokens`` (n, 1 + H, 2 sd + A + 1) and
+    ``targets`` (n, A) fp32 -- what the training step packs from a dataset of these samples -- and, with
+    ``outputs``, ``opt_action`` (n) int32 and the task itself: ``means`` / ``probs`` (n, A) float64 for a
+    bandit, ``goal`` (n, 2), ``perm`` (n, 5) and ``query`` (n, 2) int32 for DarkRoom, ``theta`` (n, d), ``means``
+    (n, A) and, under the uniform rollin, ``probs`` (n, A) float64 for the linear bandit."""
     dev, n = device(), int(n)
     sd, A, T = env.state_dim, env.action_dim, 1 + env.H
     out = dict(tokens=torch.empty((n, T, 2 * sd + A + 1), dtype=torch.float32, device=dev),
@@ -413,13 +444,18 @@ def fresh_batch(env, seed, first_task, n, outputs=True):
         if env.kind == _lib.FRESH_BANDIT:
             out.update(means=torch.empty((n, A), dtype=torch.float64, device=dev),
                        probs=torch.empty((n, A), dtype=torch.float64, device=dev))
+        elif env.kind == FreshEnv.LINEAR:
+            out.update(theta=torch.empty((n, env.lin_d), dtype=torch.float64, device=dev),
+                       means=torch.empty((n, A), dtype=torch.float64, device=dev))
+            if env.rollin == _lib.FRESH_LINEAR_UNIFORM:
+                out["probs"] = torch.empty((n, A), dtype=torch.float64, device=dev)
         else:
             out.update(goal=torch.empty((n, 2), dtype=torch.int32, device=dev),
                        perm=torch.empty((n, 5), dtype=torch.int32, device=dev),
                        query=torch.empty((n, 2), dtype=torch.int32, device=dev))
     d = _lib.TrainDesc(1, E, sd, A, T, n, T, 0, 0.0, 0, 0)  # the generator reads state_dim, action_dim, batch, window
     args = env.args(seed, first_task, out)
-    _lib.call("dpt_fresh_batch", ctypes.byref(d), ctypes.byref(args), n, _p(out["tokens"]), _p(out["targets"]),
+    _lib.call(env.calls["batch"], ctypes.byref(d), ctypes.byref(args), n, _p(out["tokens"]), _p(out["targets"]),
               _stream())
     return out
 

@@ -256,6 +256,28 @@ SIGNATURES["dpt_fresh_eval_loss"] = (_i32, [_train_desc_p, _fresh_args_p, _i32, 
                                             _c_void_p])
 
 
+FRESH_LINEAR_THOMPSON = 0  # dpt_fresh_linear_args.rollin
+FRESH_LINEAR_UNIFORM = 1
+FRESH_LINEAR_CHUNK = 32  # kLinChunk of csrc/dpt_fresh_linear.hip: the Thompson rollin's steps per chunk
+FRESH_LINEAR_MAX_D = 8   # kMaxD
+
+
+class FreshLinearArgs(ctypes.Structure):
+    """dpt_fresh_linear_args: the linear bandit's fresh-task samples first_task .. first_task + batch - 1."""
+    _fields_ = [("rollin", _i32), ("dim", _i32), ("lin_d", _i32), ("H", _i32), ("var", _f64), ("seed", _u64),
+                ("first_task", _i64), ("arms", _c_void_p), ("theta_out", _c_void_p), ("means_out", _c_void_p),
+                ("probs_out", _c_void_p), ("opt_action_out", _c_void_p)]
+
+
+_fresh_linear_args_p = ctypes.POINTER(FreshLinearArgs)
+SIGNATURES["dpt_fresh_linear_batch"] = (_i32, [_train_desc_p, _fresh_linear_args_p, _i32, _c_void_p, _c_void_p,
+                                               _c_void_p])
+SIGNATURES["dpt_fresh_linear_step"] = (_i32, [_train_desc_p, _fresh_linear_args_p, _i32, _c_void_p, _c_void_p,
+                                              _c_void_p, ctypes.POINTER(AdamWArgs), _c_void_p, _c_void_p, _c_void_p])
+SIGNATURES["dpt_fresh_linear_eval_loss"] = (_i32, [_train_desc_p, _fresh_linear_args_p, _i32, _c_void_p, _c_void_p,
+                                                   _c_void_p, _c_void_p])
+
+
 INTERACTIVE_ACCUMULATE = 1  # dpt_interactive_args.flags: dblob += the chunk's gradient
 INTERACTIVE_FULL_WIDTH = 2  # the last block at full width (no DPT_TRAIN_LAST_LOSS); for A/B runs
 

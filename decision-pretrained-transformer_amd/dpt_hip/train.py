@@ -579,7 +579,8 @@ def fresh_dataset(first_task, n, env, seed):
 
 
 class FreshTrainer(_TrainerCore):
-    """The pretraining step on fresh tasks (train_fresh.py; dpt_fresh_step): no dataset -- each step
+    """The pretraining step on fresh tasks (train_fresh.py; dpt_fresh_step, or dpt_fresh_linear_step for
+    ``FreshEnv.linear_bandit``: the env names its entry points): no dataset -- each step
     generates its batch on the device (``dpt_hip.FreshEnv``: the task, the behaviour policy, the rollin,
     the query and the label, all from Philox(``seed``) and the sample's global index), then forward, summed
     cross-entropy, backward and AdamW, the launches of ``Trainer.step`` after its pack.  ``step`` takes the
@@ -619,7 +620,7 @@ class FreshTrainer(_TrainerCore):
         args = self.env.args(self.seed, self.first_task)
         self.steps += 1
         try:
-            _lib.call("dpt_fresh_step", ctypes.byref(d), ctypes.byref(args), batch, *self.state.ptrs(),
+            _lib.call(self.env.calls["step"], ctypes.byref(d), ctypes.byref(args), batch, *self.state.ptrs(),
                       ctypes.byref(self._adamw_args()), _p(self._ws), _p(self.loss), _stream())
         except Exception:
             self.steps -= 1  # rejected on the host before any launch
@@ -639,7 +640,7 @@ class FreshTrainer(_TrainerCore):
             b = min(int(batch), int(n) - lo)
             d = self._desc(b, dropout_seed)
             args = env.args(seed, int(first_task) + lo)
-            _lib.call("dpt_fresh_eval_loss", ctypes.byref(d), ctypes.byref(args), b, _p(self.state.blob),
+            _lib.call(env.calls["eval_loss"], ctypes.byref(d), ctypes.byref(args), b, _p(self.state.blob),
                       _p(self._ws), _p(self.loss), _stream())
 
     def sync_to_model(self):

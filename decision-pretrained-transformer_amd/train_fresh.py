@@ -13,6 +13,13 @@ file, log lines, loss plot, checkpoint schedule and checkpoint names are train.p
 flags loads the result -- and a train.py checkpoint with equal flags is overwritten.  ``--hists``,
 ``--samples`` and ``--shuffle`` only name the file: fresh tasks leave nothing to repeat, and the rollin
 steps are i.i.d., so permuting them changes nothing in law.
+
+``--env linear_bandit`` needs ``--data_type thompson`` or ``--data_type uniform`` (collect_data.py's two
+data types; it collects 'thompson').  The two are different training distributions, hence the opt-in:
+'thompson' is the adaptive Thompson-sampling rollin of collect_data.py run on the device inside the step
+(equal to collect_data.py's in law, not bit for bit: the tasks are other draws), 'uniform' the bandit's i.i.d.
+behaviour policy.  The arms are collect_data.py's (``RandomState(1234)``, ``--dim`` x ``--lin_d``), the file
+names and the extra checkpoint every 10 epochs are train.py's, and ``--shuffle`` is refused as train.py refuses it.
 """
 import argparse
 import hashlib
@@ -27,7 +34,7 @@ from dpt_hip import FreshEnv
 from dpt_hip.train import FreshTrainer
 from models.net import Transformer
 from train_common import LossLog, set_seeds
-from utils import build_bandit_model_filename, build_darkroom_model_filename
+from utils import build_bandit_model_filename, build_darkroom_model_filename, build_linear_bandit_model_filename
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
@@ -55,15 +62,25 @@ def main(argv=None):
     common_args.add_train_args(parser)
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--batch", type=int, default=64)
+    parser.add_argument("--data_type", choices=["thompson", "uniform"], default=None,
+                        help="linear_bandit only: the rollin, collect_data.py's data types")
     args = vars(parser.parse_args(argv))
     print("Args: ", args)
 
     env, n_envs, horizon, dim = args["env"], args["envs"], args["H"], args["dim"]
     lr, shuffle, seed, batch = args["lr"], args["shuffle"], args["seed"], args["batch"]
-    var, cov = args["var"], args["cov"]
+    var, cov, lin_d, data_type = args["var"], args["cov"], args["lin_d"], args["data_type"]
     if env == "linear_bandit":
-        raise NotImplementedError("linear_bandit: its rollin is an adaptive Thompson run (a chain through "
-                                  "dpt_rollout_policy), not i.i.d. draws; use collect_data.py and train.py")
+        if data_type is None:
+            raise NotImplementedError("linear_bandit: collect_data.py's rollin is an adaptive Thompson run, not "
+                                      "i.i.d. draws: a training distribution of its own.  Choose it with "
+                                      "--data_type thompson (run on the device inside the step), or the i.i.d. "
+                                      "--data_type uniform; or use collect_data.py and train.py")
+        if shuffle:
+            raise Exception("Are you sure you want to shuffle on the linear bandit? Data collected from an adaptive "
+                            "algorithm in a stochastic setting can bias the learner if shuffled.")
+    elif data_type is not None:
+        raise ValueError(f"--data_type {data_type} belongs to --env linear_bandit, not to {env}")
     if batch < 1:
         raise ValueError(f"--batch {batch}")
 
@@ -79,6 +96,12 @@ def main(argv=None):
         model_config.update({"var": var, "cov": cov})
         filename = build_bandit_model_filename(env, model_config)
         train_env = test_env = FreshEnv.bandit(dim, horizon, var, "uniform" if env == "bandit" else "bernoulli")
+    elif env == "linear_bandit":
+        state_dim, action_dim = 1, dim
+        model_config.update({"lin_d": lin_d, "var": var, "cov": cov})
+        filename = build_linear_bandit_model_filename(env, model_config)
+        arms = np.random.RandomState(seed=1234).normal(size=(dim, lin_d)) / np.sqrt(lin_d)  # collect_data.py's
+        train_env = test_env = FreshEnv.linear_bandit(arms, horizon, var, data_type)
     elif env.startswith("darkroom"):
         state_dim, action_dim = 2, 5
         filename = build_darkroom_model_filename(env, model_config)
@@ -119,7 +142,7 @@ def main(argv=None):
         printw(f"\tTrain loss: {train_loss[-1]}")
         printw(f"\tTrain time: {time.time() - start_time}")
 
-        if (epoch + 1) % 50 == 0:
+        if (epoch + 1) % 50 == 0 or (env == "linear_bandit" and (epoch + 1) % 10 == 0):
             torch.save(trainer.sync_to_model().state_dict(), f"trained_models/{filename}_epoch{epoch + 1}.pt")
 
         printw.report(epoch, test_loss, train_loss)

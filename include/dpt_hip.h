@@ -64,7 +64,8 @@ extern "C" {
  * dpt_exploit_eval); the interactive DarkRoom training step (dpt_mdp_pack, dpt_darkroom_act_step,
  * dpt_interactive_mdp_workspace_numel, dpt_interactive_mdp_grad); the in-episode DarkRoom rollout in one
  * launch (dpt_rollout_darkroom_episode); the fresh-task generator and its training step (DPT_STREAM_TASK,
- * dpt_fresh_args, dpt_fresh_batch, dpt_fresh_step, dpt_fresh_eval_loss) */
+ * dpt_fresh_args, dpt_fresh_batch, dpt_fresh_step, dpt_fresh_eval_loss) and its linear-bandit twin
+ * (dpt_fresh_linear_args, dpt_fresh_linear_batch, dpt_fresh_linear_step, dpt_fresh_linear_eval_loss) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -94,7 +95,10 @@ extern "C" {
  *   bandit, A arms:  k in [0, A): means[k] = the 53-bit uniform;  A + k: e_k = -log(1 - uniform), the
  *                    Gamma(1) variates of Dirichlet(1_A);  2 A: word 0 -> index into the 11-point cov
  *                    grid, word 1 -> the point-mass arm (multiply-shift, as every integer draw)
- *   DarkRoom:        0: word 0 -> index into the goal list, word 1 -> index into the permutation list */
+ *   DarkRoom:        0: word 0 -> index into the goal list, word 1 -> index into the permutation list
+ *   linear bandit (dpt_fresh_linear_batch), A arms, d features:  p in [0, d): theta[p] = the normal / sqrt(d);
+ *                    'uniform' rollin only, the bandit's policy draws moved behind theta:  d + k: e_k;
+ *                    d + A: word 0 -> index into the cov grid, word 1 -> the point-mass arm */
 #define DPT_STREAM_TASK 5
 #define DPT_STREAM_POLICY 16/* + arm index: baseline-policy draws (Thompson posterior samples) */
 
@@ -622,6 +626,59 @@ int dpt_fresh_step(const dpt_train_desc* desc_host, const dpt_fresh_args* args_h
 /* dpt_train_eval_loss on generated samples: forward only, desc.dropout active, the loss alone. */
 int dpt_fresh_eval_loss(const dpt_train_desc* desc_host, const dpt_fresh_args* args_host, int32_t batch,
                         const float* blob, float* workspace, double* loss_acc, void* stream);
+
+/* ------------------------------------------------------------------ fresh-task training step: the linear bandit
+ * The same for the linear bandit (envs/bandit_env.py LinearBanditEnv; collect_data.py
+ * generate_linear_bandit_histories): desc.state_dim 1, dim = desc.action_dim = A <= 32 arms with the caller's
+ * features arms (A, lin_d) fp64 on the device, lin_d <= 8.  Task first_task + b:
+ *   theta[p] = normal(seed, (p, task, DPT_STREAM_TASK)) / sqrt((double)lin_d)
+ *   means[k] = ((arms[k][0] theta[0]) + arms[k][1] theta[1]) + ...   (fp64, multiply then add, index order)
+ * the label = the one-hot of the first argmax of means, row 0 = [1 | 0 ...] and row 1 + h =
+ * [1 | onehot(a_h) | 1 | float(r_h)] with r_h = means[a_h] + (0.0 + var normal(seed, (h, task,
+ * DPT_STREAM_REWARD))), the rewards of a Gaussian bandit.
+ * rollin DPT_FRESH_LINEAR_THOMPSON (collect_data.py rollin_linear_bandit_vec: ThompsonSamplingPolicy(std=var,
+ * sample=True, prior_mean=0, prior_var=1); adaptive): per arm the count n_k, the reward sum S_k (added in time
+ * order), the posterior mean m_k and std s_k, 0 and 1 before any pull.  At step h
+ *   v_k = m_k + s_k normal(seed, (h, task, DPT_STREAM_POLICY + k)),  a_h = the first index of max v,
+ * and then for a = a_h, variance = var var:  n_a += 1;  S_a += r_h;  w = variance / (variance + n_a 1.0);
+ *   m_a = (1.0 - w) (S_a / n_a);  s_a = sqrt(1.0 / (1.0 + n_a / variance))
+ * -- update_posterior_all with the running sum over the count where the reference takes np.mean.  The
+ * keying is dpt_rollout_policy's at counter 0: that kernel (DPT_POLICY_THOMPSON, sample 1, ts_std var, prior
+ * 0 / 1) on means_out sees the same normals, and gives the same rows wherever the two means leave the argmax
+ * alone.  O(H) per task.  var > 0.
+ * rollin DPT_FRESH_LINEAR_UNIFORM (data_type 'uniform'; i.i.d. steps): dpt_fresh_batch's bandit behaviour
+ * policy and steps (DPT_STREAM_ROLLIN / DPT_STREAM_REWARD at counter h), its policy draws at the task
+ * counters above.
+ * Optional outputs (NULL: not written): theta_out (batch, lin_d), means_out (batch, A), probs_out (batch, A;
+ * uniform rollin only) fp64, opt_action_out (batch) int32.                                        */
+#define DPT_FRESH_LINEAR_THOMPSON 0
+#define DPT_FRESH_LINEAR_UNIFORM 1
+typedef struct dpt_fresh_linear_args {
+    int32_t rollin;         /* DPT_FRESH_LINEAR_THOMPSON / DPT_FRESH_LINEAR_UNIFORM             */
+    int32_t dim;            /* arms A                                                           */
+    int32_t lin_d;          /* features per arm                                                 */
+    int32_t H;              /* rollin steps: desc.window = 1 + H                                */
+    double var;             /* reward noise std (and the Thompson policy's std)                 */
+    uint64_t seed;          /* Philox key                                                       */
+    int64_t first_task;     /* global index of sample 0                                         */
+    const double* arms;     /* (dim, lin_d) fp64, device                                        */
+    double* theta_out;
+    double* means_out;
+    double* probs_out;
+    int32_t* opt_action_out;
+} dpt_fresh_linear_args;
+/* the generator alone, as dpt_fresh_batch.  Host-side checks fail before the launch: DPT_EINVAL for a null
+ * desc / args / tokens / targets / arms, batch outside 1..desc.batch, desc.window != 1 + H, H < 0, state_dim
+ * != 1, action_dim != dim, dim < 1, lin_d < 1, an unknown rollin, var < 0 or not finite, var == 0 with the
+ * Thompson rollin; DPT_EUNSUPPORTED for dim > 32 or lin_d > 8. */
+int dpt_fresh_linear_batch(const dpt_train_desc* desc_host, const dpt_fresh_linear_args* args_host, int32_t batch,
+                           float* tokens, float* targets, void* stream);
+/* dpt_fresh_step / dpt_fresh_eval_loss with this generator: the same chain, workspace and checks. */
+int dpt_fresh_linear_step(const dpt_train_desc* desc_host, const dpt_fresh_linear_args* args_host, int32_t batch,
+                          float* blob, float* m, float* v, const dpt_adamw_args* adamw_host, float* workspace,
+                          double* loss_acc, void* stream);
+int dpt_fresh_linear_eval_loss(const dpt_train_desc* desc_host, const dpt_fresh_linear_args* args_host,
+                               int32_t batch, const float* blob, float* workspace, double* loss_acc, void* stream);
 
 /* ------------------------------------------------------------------ interactive training step
  * One episode of train_interactive.py:92-143 (the on-policy variant: sample fresh bandits, roll the
