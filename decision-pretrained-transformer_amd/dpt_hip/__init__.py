@@ -514,7 +514,15 @@ def rollout_policy(policy, means, H, var, bandit_type=BANDIT_GAUSSIAN, online=Tr
                    ts_std=0.1, ts_prior_mean=0.5, ts_prior_var=1 / 12.0, arms=None, seed=0, first_task=0,
                    noise=None, policy_noise=None, ctx_actions=None, ctx_rewards=None, counter=0):
     """Fused classical-policy rollout (dpt_rollout_policy); optional prefix context (N, C).
-    ``counter``: the Philox step counter of step 0 (step h draws at counter + h)."""
+    ``counter``: the Philox step counter of step 0 (step h draws at counter + h).
+    ``ctx_actions`` must lie in [0, A): the kernel indexes its LDS tables by them unchecked.  A host
+    array is checked here (ValueError); a device tensor is the caller's to keep in range."""
+    if ctx_actions is not None and not isinstance(ctx_actions, torch.Tensor):
+        ca = np.asarray(ctx_actions)
+        n_arms = int(means.shape[1]) if isinstance(means, torch.Tensor) else int(np.asarray(means).shape[1])
+        if ca.size and (ca.min() < 0 or ca.max() >= n_arms):
+            raise ValueError(f"ctx_actions holds arm indices in [{ca.min()}, {ca.max()}]; the {n_arms} arms are "
+                             f"0..{n_arms - 1}")
     dev = device()
     means_d = _dev(means, torch.float64, dev)
     N, A = means_d.shape

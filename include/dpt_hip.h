@@ -363,7 +363,9 @@ typedef struct dpt_policy_rollout_args {
     int32_t step0;              /* Philox step counter of step 0: step h draws at step0 + h, so a
                                  * per-step call (H = 1, step0 = h) draws what the fused launch
                                  * (step0 = 0) draws at step h */
-    const int32_t* ctx_actions; /* (N, C) arm indices */
+    const int32_t* ctx_actions; /* (N, C) arm indices.  Precondition: every value in [0, A).  They are
+                                 * device memory, so dpt_rollout_policy cannot check them; a value
+                                 * outside the range indexes the kernel's LDS tables out of range */
     const double* ctx_rewards;  /* (N, C) */
 } dpt_policy_rollout_args;
 
