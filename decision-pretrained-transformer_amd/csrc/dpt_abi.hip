@@ -180,8 +180,12 @@ int dpt_tuning_set(int32_t key, int64_t value) {
         return DPT_OK;
     }
     if (key == DPT_TUNE_BLOCK0_MFMA) {
-        DPT_REQUIRE(value == 0 || value == 1, "block-0 MFMA %lld: 0 or 1", (long long)value);
-        return set_block0_mfma((int)value);
+        if (value != 0) {
+            set_error(DPT_EUNSUPPORTED, "DPT_TUNE_BLOCK0_MFMA %lld: only 0 (block 0 on the vector ALUs; the "
+                      "matrix-core form was retired)", (long long)value);
+            return DPT_EUNSUPPORTED;
+        }
+        return DPT_OK;
     }
     if (key == DPT_TUNE_YCACHE_BITS) {
         DPT_REQUIRE(set_ycache_bits((int)value) == DPT_OK, "y cache bits %lld: 24 or 32", (long long)value);

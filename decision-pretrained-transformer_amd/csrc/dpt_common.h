@@ -439,7 +439,6 @@ int launch_derive_l0(const ModelView&, float*, hipStream_t);
 int64_t l0_numel(int n_layer);
 int set_decode_tile(int);
 int set_cache_budget(int64_t);
-int set_block0_mfma(int);
 int set_ycache_bits(int);
 // dpt_env.hip
 int launch_bandit_step(const double*, int, int, const int32_t*, int, double, const double*, uint64_t, uint64_t,

@@ -98,11 +98,6 @@ struct Smem {
     float tok[kM][kMaxF];        // packed token features of the current position
 };
 static_assert(sizeof(Smem) % 16 == 0, "parameter block must start 16-B aligned");
-static_assert(sizeof(Smem::part) >= 8 * 8 * 64 * sizeof(float), "l0_tiles partials (8 waves x 8 tasks x kL0Part) live in part");
-
-// Columns of l0_tiles' per-task constants (alpha, gamma, beta[0..A]): one or two
-// 16-column MFMA tiles of the u phase.
-__host__ __device__ constexpr int l0_cols(int A) { return A + 3 <= 16 ? 16 : 32; }
 
 // Small parameters copied to LDS once per launch (offsets in floats).
 struct PLay {
@@ -135,11 +130,8 @@ __host__ inline size_t decode_smem_bytes(const ModelView& M) {
 // for k < A and base[A] = w_s + emb_b (the query token), then g0 and bvp of
 // every layer (kE floats per layer each) and the folded matrices Wvp and G.
 struct RolloutLDS {
-    int means, base, g0, bvp, wvp, G, gx, gx0, total;
-    // l0m: block 0 on the matrix cores (l0_tiles) -- its extra u-projection columns
-    // gx [E][C] (alpha, gamma, beta[0..A] of l0_tiles as linear maps of xn) and gx0 [C],
-    // C = l0_cols(A)
-    __host__ __device__ static RolloutLDS make(int A, int L, bool with_G = true, bool l0m = false) {
+    int means, base, g0, bvp, wvp, G, total;
+    __host__ __device__ static RolloutLDS make(int A, int L, bool with_G = true) {
         RolloutLDS r;
         r.means = 0;               // the tile's arm means, double [kM][A]
         r.base = 2 * kM * A;
@@ -147,15 +139,13 @@ struct RolloutLDS {
         r.bvp = r.g0 + L * kE;
         r.wvp = r.bvp + L * kE;  // Wv Wproj of every layer (c_proj's B operand, read from LDS)
         r.G = r.wvp + L * kE * kE;  // Wq Wk^T of every layer (the u projection's B operand)
-        r.gx = r.G + (with_G ? L * kE * kE : 0);
-        r.gx0 = r.gx + kE * l0_cols(A);
-        r.total = l0m ? r.gx0 + l0_cols(A) : r.gx;
+        r.total = r.G + (with_G ? L * kE * kE : 0);
         return r;
     }
 };
 
-__host__ inline size_t rollout_smem_bytes(const ModelView& M, bool with_G, bool l0m = false) {
-    return decode_smem_bytes(M) + sizeof(float) * (size_t)RolloutLDS::make(M.A, M.n_layer, with_G, l0m).total;
+__host__ inline size_t rollout_smem_bytes(const ModelView& M, bool with_G) {
+    return decode_smem_bytes(M) + sizeof(float) * (size_t)RolloutLDS::make(M.A, M.n_layer, with_G).total;
 }
 
 template <int NT>
@@ -582,220 +572,6 @@ __device__ __attribute__((always_inline)) inline float4 attend_l0(const float4* 
     return res;
 }
 
-// Block-0 attention of a whole tile on the matrix cores (L0M: tile of 8 tasks, NA =
-// A + 1 token kinds).  With TokRec (a_p, r_p, mean_p, rstd_p), gu = g * u and
-// x_p = r_p w_r + base[a_p] + wpe[p] (attend_l0):
-//   score_p = rstd_p ((x_p - mean_p) . gu) = rstd_p (r_p alpha + beta[a_p] + wpe[p] . gu - mean_p gamma)
-//   sum_p w_p (x_p - mean_p) = (sum w r) w_r + sum_k (sum_{a_p = k} w_p) base[k] + sum_p w_p wpe[p] - (sum w mean) 1
-// with alpha = w_r . gu, beta[k] = base[k] . gu, gamma = sum gu (per task and step: the
-// u projection's extra columns, kept in S.vcur) and w_p = P_p rstd_p.  The only
-// per-position vector terms involve wpe, which every task shares: the scores are one
-// [16 positions x 32] x [32 x 16 tasks] MFMA product per 16-position tile and the
-// weighted wpe sum one [32 x 16 positions] x [16 x 16 tasks] product; everything else
-// is per-(position, task) scalar work, one element per lane and register.  Wave w
-// takes the tiles w, w + 8, ...; its partial softmax state per task (m, l, the scalar
-// sums, the arm sums and the wpe sum) goes to part[w][task][kL0Part] for l0_merge.
-constexpr int kL0Part = 64;  // floats per (wave, task) partial of l0_tiles (36 + NA <= 64)
-
-template <int NA, int TILE>
-__device__ __attribute__((always_inline)) inline void l0_tiles(const float* __restrict__ rec_base,
-                                                               int ntask, int pos, const float* __restrict__ wpe,
-                                                               const float* q, const float* cst, const float* lng,
-                                                               float* part, int wave, int lane) {
-    const int n = lane & 15, j = lane >> 4;
-    const bool tv = n < ntask;  // lanes of columns >= the tile's live tasks carry zeros
-    const float scale2 = 0.17677669529663687f * 1.4426950408889634f;  // 32 ** -0.5 * log2(e)
-    // B operand of the score product: gu[task n][dim 8j + s] (k-step s takes dims {8j + s})
-    float gb[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) gb[s] = tv ? lng[8 * j + s] * q[n * kE + 8 * j + s] : 0.f;
-    const float* cn = cst + (tv ? n : 0) * kE;
-    const float alpha = cn[0], gamma = cn[1];
-    // this lane's task's records, TILE float4 apart per position (tokrec)
-    const float4* rec = reinterpret_cast<const float4*>(rec_base) + (tv ? n : 0);
-    float m = -1e30f, l = 0.f, sr = 0.f, sm = 0.f;
-    float W[NA];
-#pragma unroll
-    for (int k = 0; k < NA; ++k) W[k] = 0.f;
-    floatx4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
-#pragma unroll 1
-    for (int p0 = 16 * wave; p0 < pos; p0 += 16 * 8) {
-        // every global load of the tile first (independent; consumed in issue order):
-        // the score operand rows, the 4 token records, the wpe operand of the output product
-        const float* wrow = wpe + (size_t)min(p0 + n, pos - 1) * kE + 8 * j;
-        const floatx4 wa0 = *reinterpret_cast<const floatx4*>(wrow);
-        const floatx4 wa1 = *reinterpret_cast<const floatx4*>(wrow + 4);
-        float4 R[4];
-        float wo0[4], wo1[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) R[r] = rec[(size_t)min(p0 + 4 * j + r, pos - 1) * TILE];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* wr = wpe + (size_t)min(p0 + 4 * j + r, pos - 1) * kE + n;
-            wo0[r] = wr[0];
-            wo1[r] = wr[16];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // scores: D[position p0 + 4j + r][task n] = wpe[p] . gu_n (two chains of 4)
-        floatx4 sa = {0.f, 0.f, 0.f, 0.f}, sb = sa;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(wa0[s], gb[s], sa, 0, 0, 0);
-            sb = __builtin_amdgcn_mfma_f32_16x16x4f32(wa1[s], gb[4 + s], sb, 0, 0, 0);
-        }
-        float beta[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) beta[r] = cn[2 + __float_as_int(R[r].x)];
-        float sc[4];
-        float mx = -1e30f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int p = p0 + 4 * j + r;
-            float t = fmaf(R[r].y, alpha, beta[r]) + (sa[r] + sb[r]);
-            t = fmaf(-R[r].z, gamma, t);
-            sc[r] = (tv && p < pos) ? (R[r].w * t) * scale2 : -INFINITY;
-            mx = fmaxf(mx, sc[r]);
-        }
-        // one running max per task: over the 4 lane groups holding its positions
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mn = fmaxf(m, mx);
-        const float corr = __builtin_amdgcn_exp2f(m - mn);
-        l *= corr;
-        sr *= corr;
-        sm *= corr;
-#pragma unroll
-        for (int k = 0; k < NA; ++k) W[k] *= corr;
-        o0 *= corr;
-        o1 *= corr;
-        m = mn;
-        float wv[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float pr = __builtin_amdgcn_exp2f(sc[r] - mn);
-            l += pr;
-            const float w = pr * R[r].w;
-            wv[r] = w;
-            sr = fmaf(w, R[r].y, sr);
-            sm = fmaf(w, R[r].z, sm);
-            const int ak = __float_as_int(R[r].x);
-#pragma unroll
-            for (int k = 0; k < NA; ++k) W[k] += (ak == k) ? w : 0.f;
-        }
-        // D2[dim 16 dt + 4j + i][task n] += sum over the tile's positions of wpe[p][dim] w[p][n]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wo0[r], wv[r], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wo1[r], wv[r], o1, 0, 0, 0);
-        }
-    }
-    // the scalar sums over the 4 lane groups of each task
-    auto red = [](float v) {
-        v += __shfl_xor(v, 16);
-        return v + __shfl_xor(v, 32);
-    };
-    l = red(l);
-    sr = red(sr);
-    sm = red(sm);
-#pragma unroll
-    for (int k = 0; k < NA; ++k) W[k] = red(W[k]);
-    if (n < 8) {
-        float* pp = part + (wave * 8 + n) * kL0Part;
-        *reinterpret_cast<floatx4*>(pp + 4 * j) = o0;
-        *reinterpret_cast<floatx4*>(pp + 16 + 4 * j) = o1;
-        if (j == 0) {
-            pp[32] = m;
-            pp[33] = l;
-            pp[34] = sr;
-            pp[35] = sm;
-#pragma unroll
-            for (int k = 0; k < NA; ++k) pp[36 + k] = W[k];
-        }
-    }
-}
-
-// Combines the 8 waves' l0_tiles partials of one task (one wave, lane (g, c) forms
-// dims 4c..4c+3), adds the current position (its x is xcur) and returns
-// o = g * (sum_p P_p rstd_p (x_p - mean_p)) + b, as attend_l0.
-template <int NA>
-__device__ __attribute__((always_inline)) inline float4 l0_merge(const float* part, int t, const float* u,
-                                                                 const float* xcur, const float* baseT,
-                                                                 const float* wr, const float* lng, const float* lnb,
-                                                                 int lane) {
-    const int g = lane >> 3, c = lane & 7;
-    const float scale2 = 0.17677669529663687f * 1.4426950408889634f;
-    float mw[8];
-    float M = -1e30f;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-        mw[w] = part[(w * 8 + t) * kL0Part + 32];
-        M = fmaxf(M, mw[w]);
-    }
-    float L = 0.f, SR = 0.f, SM = 0.f;
-    float Wk[NA];
-#pragma unroll
-    for (int k = 0; k < NA; ++k) Wk[k] = 0.f;
-    f2 olo = {0.f, 0.f}, ohi = {0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-        const float* pp = part + (w * 8 + t) * kL0Part;
-        const float sw = __builtin_amdgcn_exp2f(mw[w] - M);
-        L = fmaf(sw, pp[33], L);
-        SR = fmaf(sw, pp[34], SR);
-        SM = fmaf(sw, pp[35], SM);
-#pragma unroll
-        for (int k = 0; k < NA; ++k) Wk[k] = fmaf(sw, pp[36 + k], Wk[k]);
-        const floatx4 o4 = *reinterpret_cast<const floatx4*>(pp + 4 * c);
-        olo = pk_fma(splat2(sw), o4.lo, olo);
-        ohi = pk_fma(splat2(sw), o4.hi, ohi);
-    }
-    // V = sum_p w_p (x_p - mean_p) over the cached positions, dims 4c..4c+3
-    const floatx4 wr4 = *reinterpret_cast<const floatx4*>(wr + 4 * c);
-    olo = pk_fma(splat2(SR), wr4.lo, olo);
-    ohi = pk_fma(splat2(SR), wr4.hi, ohi);
-#pragma unroll
-    for (int k = 0; k < NA; ++k) {
-        const floatx4 b4 = *reinterpret_cast<const floatx4*>(baseT + k * kE + 4 * c);
-        olo = pk_fma(splat2(Wk[k]), b4.lo, olo);
-        ohi = pk_fma(splat2(Wk[k]), b4.hi, ohi);
-    }
-    olo -= splat2(SM);
-    ohi -= splat2(SM);
-    // the current position (every lane computes it; its group sums are 8-lane DPP)
-    const floatx4 u4 = *reinterpret_cast<const floatx4*>(u + 4 * c);
-    const floatx4 g4 = *reinterpret_cast<const floatx4*>(lng + 4 * c);
-    const floatx4 gu = g4 * u4;
-    const floatx4 x = *reinterpret_cast<const floatx4*>(xcur + 4 * c);
-    const float mean = dpp_sum8((x.x + x.y) + (x.z + x.w)) * (1.0f / kE);
-    floatx4 d;
-    d.lo = x.lo - splat2(mean);
-    d.hi = x.hi - splat2(mean);
-    float vv = d.x * d.x;
-    vv = fmaf(d.y, d.y, vv);
-    vv = fmaf(d.z, d.z, vv);
-    vv = fmaf(d.w, d.w, vv);
-    float dg = d.x * gu.x;
-    dg = fmaf(d.y, gu.y, dg);
-    dg = fmaf(d.z, gu.z, dg);
-    dg = fmaf(d.w, gu.w, dg);
-    vv = dpp_sum8(vv);
-    dg = dpp_sum8(dg);
-    const float rc = __builtin_amdgcn_rsqf(vv * (1.0f / kE) + 1e-5f);
-    const float sc = (rc * dg) * scale2;
-    const float mn = fmaxf(M, sc);
-    const float corr = __builtin_amdgcn_exp2f(M - mn);
-    const float pr = __builtin_amdgcn_exp2f(sc - mn);
-    L = L * corr + pr;
-    const f2 wc = splat2(pr * rc);
-    olo = pk_fma(wc, d.lo, olo * splat2(corr));
-    ohi = pk_fma(wc, d.hi, ohi * splat2(corr));
-    const f2 inv = splat2(1.0f / L);
-    const floatx4 b4 = *reinterpret_cast<const floatx4*>(lnb + 4 * c);
-    const f2 rlo = pk_fma(g4.lo, olo * inv, b4.lo), rhi = pk_fma(g4.hi, ohi * inv, b4.hi);
-    (void)g;
-    return make_float4(rlo.x, rlo.y, rhi.x, rhi.y);
-}
-
 // The rollout's c_proj + residual + ln_2 for one task inside its attention wave (no
 // extra phase or barrier): lane (c = l & 7, g = l >> 3) holds attention dims
 // o4 = o[4c..4c+3] and forms the partial outputs j = 4g..4g+3 over them from the
@@ -862,13 +638,11 @@ __device__ inline void zero_smem(Smem& S) {
 // position, layer l's K slot) instead of K and V (256 B): q . k_p = y_p . u +
 // const with u = Wk q = xn G + g0, and sum_p P_p v_p = (sum_p P_p y_p) Wv + bv, so
 // the same y stream serves as keys and values.  D is the RolloutLDS block.
-// L0M (bandit rollout, tile 8): block 0's attention on the matrix cores for NA = L0M
-// token kinds (l0_tiles + l0_merge) instead of one wave per task (attend_l0).
 // YQ (bandit rollout): blocks >= 1 cache the normalised row yhat_p = (h_p - mean_p) rstd_p as
 // packed 24-bit fixed point (96 B per position, dpt_ycache.h) and run on the second set of
 // folded weights (derive_l0_kernel), which carries ln_1's g and b: y_p . u = yhat_p . (g * u) +
 // b . u (the second term shifts every score alike) and sum_p P_p y_p = g * (sum_p P_p yhat_p) + b.
-template <int TILE, bool L0R = false, bool GL = false, int L0M = 0, bool YQ = false>
+template <int TILE, bool L0R = false, bool GL = false, bool YQ = false>
 __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, const ModelView& M,
                                 float* __restrict__ kv, int N, int max_pos, int tile0, int pos, float wpe_j,
                                 const float* D = nullptr, int pin = 0, int pin_x = 0) {
@@ -929,22 +703,6 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
                     const int t = kq * 4 + r;
                     if (t < TILE) S.q[t][col] = acc[r] + bias;
                 }
-            } else if (L0M && li == 0 && wave < 2 + l0_cols(L0M - 1) / 16) {
-                // l0_tiles' per-task constants (alpha, gamma, beta[k]) = xn gx + gx0 -> S.vcur
-                constexpr int C = l0_cols(L0M - 1);
-                const RolloutLDS rl = RolloutLDS::make(M.A, M.n_layer, GL, true);
-                const int col = (wave - 2) * 16 + i16;
-                floatx4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int s = 0; s < 8; ++s)
-                    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(S.xn[i16][4 * s + kq], D[rl.gx + (4 * s + kq) * C + col],
-                                                               acc, 0, 0, 0);
-                const float bias = D[rl.gx0 + col];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int t = kq * 4 + r;
-                    if (t < TILE) S.vcur[t][col] = acc[r] + bias;
-                }
             }
         } else if (wave < 6) {
         // c_attn: [16 x 32] x [32 x 96] -> q | k | v, one 16-column tile per wave
@@ -981,14 +739,6 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
         }
         bar_lds();
         DPT_STAMP(1);
-        if constexpr (L0M > 0) {
-            if (li == 0) {  // block 0: every wave takes a share of the tile's cached positions
-                l0_tiles<L0M, TILE>(tokrec(kv, max_pos, tile0, 0, TILE, 0), min(TILE, N - tile0),
-                              pos, M.wpe, &S.q[0][0], &S.vcur[0][0], PL + PLay::ln1_g,
-                              &S.part[0][0][0], wave, lane);
-                bar_lds();
-            }
-        }
         // the streaming phase yields issue slots to the other workgroup's latency-bound dense
         // phases (s_setprio; -0.5 % at config 2, -1 % on the linear config)
         if (L0R) __builtin_amdgcn_s_setprio(0);
@@ -1006,10 +756,7 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
                 if (L0R) {
                     const RolloutLDS rl = RolloutLDS::make(M.A, M.n_layer);
                     const float4 o4 =
-                        (L0M > 0 && l0) ? l0_merge<(L0M > 0 ? L0M : 1)>(&S.part[0][0][0], wave, S.q[wave], S.x[wave], D + rl.base,
-                                                             P + pl.emb_w + (2 + M.A) * kE, PL + PLay::ln1_g,
-                                                             PL + PLay::ln1_b, lane)
-                        : l0 ? attend_l0<TILE>(reinterpret_cast<const float4*>(tokrec(kv, max_pos, tile0, 0, TILE, wave)), M.wpe, pos, S.q[wave], S.x[wave],
+                        l0 ? attend_l0<TILE>(reinterpret_cast<const float4*>(tokrec(kv, max_pos, tile0, 0, TILE, wave)), M.wpe, pos, S.q[wave], S.x[wave],
                                        D + rl.base, P + pl.emb_w + (2 + M.A) * kE, PL + PLay::ln1_g,
                                        PL + PLay::ln1_b, nullptr, lane)
                            // scores y_p . u, output sum_p P_p y_p; y_pos is in S.kcur
@@ -1031,12 +778,12 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
         // c_proj + residual + ln_2, one wave: both 16-column tiles, rows reduced over 16 lanes
         // (the rollout did this per task in the attention phase)
         if (!L0R && wave == kProjWave) {
-            const float* B = L0R ? D + RolloutLDS::make(M.A, M.n_layer).wvp + li * kE * kE : W + LayerOff::proj_w;
+            const float* B = W + LayerOff::proj_w;
             float w0[8], w1[8];
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                w0[s] = L0R ? B[(4 * s + kq) * kE + i16] : __ldg(B + (size_t)(4 * s + kq) * kE + i16);
-                w1[s] = L0R ? B[(4 * s + kq) * kE + 16 + i16] : __ldg(B + (size_t)(4 * s + kq) * kE + 16 + i16);
+                w0[s] = __ldg(B + (size_t)(4 * s + kq) * kE + i16);
+                w1[s] = __ldg(B + (size_t)(4 * s + kq) * kE + 16 + i16);
             }
             floatx4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1046,7 +793,7 @@ __device__ void decode_position(Smem& S, const float* P, const ParamLDS& pl, con
                 a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, w1[s], a1, 0, 0, 0);
             }
             const int c0 = i16, c1 = 16 + i16;
-            const float* pb = L0R ? D + RolloutLDS::make(M.A, M.n_layer).bvp + li * kE : PL + PLay::proj_b;
+            const float* pb = PL + PLay::proj_b;
             const float b0 = pb[c0], b1 = pb[c1];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -1336,15 +1083,15 @@ __device__ inline int select_rollout(const float* logits, int A, int sample, dou
 // The bandit online loop (evals/eval_bandit.py:70-89) for one tile of tasks,
 // all H steps: decode -> select -> env step -> append transition.
 // YQ: the packed 24-bit y cache (rollout_bandit_kernel); otherwise fp32 rows (rollout_bandit_f32_kernel)
-template <int TILE, bool GL, int L0M, bool YQ>
+template <int TILE, bool GL, bool YQ>
 __device__ __attribute__((always_inline)) inline void rollout_bandit_body(const ModelView& M, const BanditRolloutParams& Pr) {
     DPT_SMEM_SETUP(TILE)
     const int tile0 = blockIdx.x * TILE;
     const int tid = threadIdx.x;
     const int A = Pr.A;
-    // block 0 runs K/V-free (attend_l0 / l0_tiles): token embedding table and folded weights in LDS
+    // block 0 runs K/V-free (attend_l0): token embedding table and folded weights in LDS
     float* D = P + pl.total;
-    const RolloutLDS rl = RolloutLDS::make(A, M.n_layer, GL, L0M > 0);
+    const RolloutLDS rl = RolloutLDS::make(A, M.n_layer, GL);
     double* means = reinterpret_cast<double*>(D + rl.means);
     for (int i = tid; i < TILE * A; i += TILE * 64) {
         const int t = i / A, k = i % A;
@@ -1369,28 +1116,6 @@ __device__ __attribute__((always_inline)) inline void rollout_bandit_body(const 
         D[rl.wvp + i] = l0w[(size_t)li * L0Off::size + L0Off::Wvp + j];
         if (GL) D[rl.G + i] = l0w[(size_t)li * L0Off::size + L0Off::G + j];
     }
-    if constexpr (L0M > 0) {
-        // l0_tiles' constants as maps of xn: column c of gx is G v_c and gx0[c] = g0 . v_c for
-        // v_0 = g * w_r (alpha), v_1 = g (gamma), v_{2+k} = g * base[k] (beta[k]); fp64 sums
-        __syncthreads();  // base[] complete
-        const float* g = P + pl.layers + PLay::ln1_g;
-        const float* wr = P + pl.emb_w + (2 + A) * kE;
-        auto v = [&](int c, int jj) -> double {
-            if (c == 0) return (double)g[jj] * wr[jj];
-            if (c == 1) return (double)g[jj];
-            if (c < 2 + L0M) return (double)g[jj] * D[rl.base + (c - 2) * kE + jj];
-            return 0.0;
-        };
-        const float* G0 = M.l0 + L0Off::G;
-        const float* g00 = M.l0 + L0Off::g0;
-        constexpr int C = l0_cols(L0M - 1);
-        for (int i = tid; i < (kE + 1) * C; i += TILE * 64) {
-            const int row = i / C, c = i % C;
-            double acc = 0.0;
-            for (int jj = 0; jj < kE; ++jj) acc += (row < kE ? (double)G0[row * kE + jj] : (double)g00[jj]) * v(c, jj);
-            D[rl.gx + i] = (float)acc;  // row kE lands in gx0 (= gx + kE * C)
-        }
-    }
     // (a_p, r_p) of this thread's task's token record of position p (TokRec)
     auto tokrec_ar = [&](int p) {
         return reinterpret_cast<float2*>(tokrec(Pr.kv, Pr.H, tile0, p, TILE, tid));
@@ -1413,7 +1138,7 @@ __device__ __attribute__((always_inline)) inline void rollout_bandit_body(const 
             const doublex2 d2 = __builtin_nontemporal_load(reinterpret_cast<const doublex2*>(draws + (size_t)h * TILE));
             dr = make_double2(d2[0], d2[1]);
         }
-        decode_position<TILE, true, GL, L0M, YQ>(S, P, pl, M, Pr.kv, Pr.N, Pr.H, tile0, h, wpe_j, D, Pr.pin, Pr.pin_x);
+        decode_position<TILE, true, GL, YQ>(S, P, pl, M, Pr.kv, Pr.N, Pr.H, tile0, h, wpe_j, D, Pr.pin, Pr.pin_x);
         // selection + env step; the outputs are stored after the barrier so that it
         // waits only for the y rows (issued phases earlier), not for these stores
         const int t = tid, task = tile0 + t;
@@ -1445,15 +1170,15 @@ __device__ __attribute__((always_inline)) inline void rollout_bandit_body(const 
 }
 
 // the default: blocks >= 1 cache packed 24-bit rows (DPT_TUNE_YCACHE_BITS = 24)
-template <int TILE, bool GL, int L0M = 0>
+template <int TILE, bool GL>
 __global__ __launch_bounds__(TILE * 64, 4) void rollout_bandit_kernel(ModelView M, BanditRolloutParams Pr) {
-    rollout_bandit_body<TILE, GL, L0M, true>(M, Pr);
+    rollout_bandit_body<TILE, GL, true>(M, Pr);
 }
 
-// fp32 rows (DPT_TUNE_YCACHE_BITS = 32: the comparison path; and block 0 on the matrix cores)
-template <int TILE, bool GL, int L0M = 0>
+// fp32 rows (DPT_TUNE_YCACHE_BITS = 32: the comparison path)
+template <int TILE, bool GL>
 __global__ __launch_bounds__(TILE * 64, 4) void rollout_bandit_f32_kernel(ModelView M, BanditRolloutParams Pr) {
-    rollout_bandit_body<TILE, GL, L0M, false>(M, Pr);
+    rollout_bandit_body<TILE, GL, false>(M, Pr);
 }
 
 // ----------------------------------------------------------------------------- host side
@@ -1554,17 +1279,11 @@ extern "C" int dpt_debug_stamps(unsigned long long* out, int n, int reset) {
 
 static int g_decode_tile = 8;  // tuning knob (dpt_tuning_set(DPT_TUNE_DECODE_TILE, 8|16))
 static int64_t g_cache_budget = DPT_DEFAULT_CACHE_BUDGET;  // DPT_TUNE_CACHE_BUDGET
-static bool g_block0_mfma = false;                         // DPT_TUNE_BLOCK0_MFMA
 static int g_ycache_bits = 24;                             // DPT_TUNE_YCACHE_BITS
 
 int set_ycache_bits(int bits) {
     if (bits != 24 && bits != 32) return DPT_EINVAL;
     g_ycache_bits = bits;
-    return DPT_OK;
-}
-
-int set_block0_mfma(int on) {
-    g_block0_mfma = on != 0;
     return DPT_OK;
 }
 
@@ -1656,11 +1375,8 @@ int launch_rollout_bandit(const ModelView& M, const dpt_bandit_rollout_args& a, 
     // G in LDS when the block still lets the tile's workgroups share a CU (two at
     // tile 8, one at tile 16); otherwise the u projection reads it from L2
     const size_t per_cu = 160 * 1024 / (g_decode_tile == 8 ? 2 : 1);
-    // block 0 on the matrix cores (l0_tiles) for the 5-arm configs at tile 8
-    // (A = 20 in this form spills at the 128-VGPR cap: its 21 arm sums; measured +17 %)
-    const bool l0m = g_block0_mfma && g_decode_tile == 8 && a.A == 5;
-    const bool gl = rollout_smem_bytes(M, true, l0m) <= per_cu;
-    sm = rollout_smem_bytes(M, gl, l0m);
+    const bool gl = rollout_smem_bytes(M, true) <= per_cu;
+    sm = rollout_smem_bytes(M, gl);
     if (sm > 160 * 1024) {
         set_error(DPT_EUNSUPPORTED, "rollout LDS %zu B > 160 KiB (n_layer=%d, action_dim=%d)", sm, M.n_layer, M.A);
         return DPT_EUNSUPPORTED;
@@ -1677,9 +1393,8 @@ int launch_rollout_bandit(const ModelView& M, const dpt_bandit_rollout_args& a, 
     P.logits_out = a.logits_out;
     P.n_layer = M.n_layer;
     P.tile = g_decode_tile;
-    // the packed 24-bit y cache unless the fp32 form is asked for; block 0 on the matrix cores is
-    // built in the fp32 form only
-    const bool packed = g_ycache_bits == 24 && !l0m;
+    // the packed 24-bit y cache unless the fp32 form is asked for
+    const bool packed = g_ycache_bits == 24;
     rollout_pin(a.N, a.H, M.n_layer, packed, &P.pin, &P.pin_x);
     const int64_t nd = (int64_t)a.N * a.H;
     hipLaunchKernelGGL(rollout_draws_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, P);
@@ -1687,9 +1402,7 @@ int launch_rollout_bandit(const ModelView& M, const dpt_bandit_rollout_args& a, 
         allow_smem(kernel, sm);
         hipLaunchKernelGGL(kernel, dim3((a.N + tile - 1) / tile), dim3(tile * 64), sm, st, M, P);
     };
-    if (l0m)
-        gl ? launch(rollout_bandit_f32_kernel<8, true, 6>, 8) : launch(rollout_bandit_f32_kernel<8, false, 6>, 8);
-    else if (!packed && g_decode_tile == 8)
+    if (!packed && g_decode_tile == 8)
         gl ? launch(rollout_bandit_f32_kernel<8, true>, 8) : launch(rollout_bandit_f32_kernel<8, false>, 8);
     else if (!packed)
         gl ? launch(rollout_bandit_f32_kernel<16, true>, 16) : launch(rollout_bandit_f32_kernel<16, false>, 16);

@@ -655,8 +655,9 @@ def set_ycache_bits(bits):
 
 
 def set_block0_mfma(on):
-    """Bandit rollout, 5 arms at tile 8: block 0's attention on the matrix cores, or one wave per
-    task on the vector ALUs (default).  Same algebra; the fp32 summation order differs."""
+    """Retired with the matrix-core form of the bandit rollout's block 0: False (one wave per task on
+    the vector ALUs, the only form) is accepted, True raises NotImplementedError (DPT_TUNE_BLOCK0_MFMA
+    accepts only 0).  Kept so that callers written for the knob get the library's error."""
     _lib.call("dpt_tuning_set", _lib.TUNE_BLOCK0_MFMA, int(bool(on)))
 
 

@@ -120,11 +120,10 @@ const char* dpt_last_error(void);
  * are re-read on-die every step; later positions stream non-temporally and do
  * not displace them).  0: every row non-temporal.  Cache policy only: results
  * are bit-identical for any value.
- * DPT_TUNE_BLOCK0_MFMA = 0 (default): dpt_rollout_bandit computes block 0's
- * attention with one wave per task on the vector ALUs; 1: for tiles of 8
- * five-arm tasks, on the matrix cores (the shared position-embedding terms as
- * MFMA products, the per-token terms as scalars).  Same algebra, different fp32
- * summation order; equal speed at config 2.
+ * DPT_TUNE_BLOCK0_MFMA = 0 (the only value): dpt_rollout_bandit computes block
+ * 0's attention with one wave per task on the vector ALUs; any other value
+ * returns DPT_EUNSUPPORTED (the matrix-core form for tiles of 8 five-arm tasks
+ * was retired: equal speed at config 2, slower at 20 arms).
  * DPT_TUNE_SELECT_FAST = 1 (default): dpt_select_action decides 5- and 20-arm
  * samples on the fp32 cdf when the uniform is more than 2^-15 from every cdf
  * edge and runs the exact fp64 cdf otherwise (the rollouts always do); 0: the
@@ -137,8 +136,7 @@ const char* dpt_last_error(void);
  * ln_1 rows of blocks >= 1 as signed 24-bit fixed point (96 B per position,
  * absolute error <= 2^-21, below the kernel's fp32 summation noise; ln_1's g and b
  * are folded into the derived weights); 32: as fp32 rows (128 B), the comparison
- * path.  Block 0 on the matrix cores (DPT_TUNE_BLOCK0_MFMA = 1) always runs the
- * fp32 form.  The workspace size (dpt_kvcache_numel) is the same for both.  */
+ * path.  The workspace size (dpt_kvcache_numel) is the same for both.  */
 #define DPT_TUNE_DECODE_TILE 1
 #define DPT_TUNE_PREFILL 2
 #define DPT_TUNE_DARKROOM_MEMO 3

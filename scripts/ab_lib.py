@@ -1,8 +1,7 @@
 """A/B of library builds (Makefile `variant`): one bandit rollout timing per library,
 each in its own process (python scripts/ab_lib.py libA.so libB.so ...; rounds alternate).
-An argument libX.so:<bytes> runs libX.so with dpt_hip.set_cache_budget(<bytes>); a suffix +b0 / +nob0
-runs it with dpt_hip.set_block0_mfma(True / False); +nows / +nomemo run DarkRoom without the
-layer-0 workspace / the logits memo (suffixes in that order: lib.so+nows+nomemo); a last suffix
+An argument libX.so:<bytes> runs libX.so with dpt_hip.set_cache_budget(<bytes>); the suffixes +nows / +nomemo
+run DarkRoom without the layer-0 workspace / the logits memo (in that order: lib.so+nows+nomemo); a last suffix
 +y32 / +y24 sets dpt_hip.set_ycache_bits (a build without that key fails when it is set).  libX.so@<file>.py
 (before any other suffix) loads that file in place of dpt_hip/train.py: an A/B of the Python layer on one library.
 Env: AB_H, AB_N, AB_A, AB_TILE, AB_ROUNDS.
@@ -531,10 +530,6 @@ def child(lib):
     for suf, bits in (("+y32", 32), ("+y24", 24)):
         if lib.endswith(suf):
             lib, ybits = lib[: -len(suf)], bits
-    b0 = None  # "libX.so+b0" / "+nob0": DPT_TUNE_BLOCK0_MFMA 1 / 0
-    for suf, on in (("+nob0", False), ("+b0", True)):
-        if lib.endswith(suf):
-            lib, b0 = lib[: -len(suf)], on
     nomemo = lib.endswith("+nomemo")  # DarkRoom with every step a window forward
     lib = lib[: -len("+nomemo")] if nomemo else lib
     nows = lib.endswith("+nows")  # DarkRoom without the per-episode layer-0 workspace
@@ -547,8 +542,6 @@ def child(lib):
     import dpt_hip
     H, N, A = (int(os.environ.get(k, d)) for k, d in (("AB_H", "500"), ("AB_N", "4096"), ("AB_A", "5")))
     dpt_hip.set_decode_tile(int(os.environ.get("AB_TILE", "8")))
-    if b0 is not None:
-        dpt_hip.set_block0_mfma(b0)
     if ybits is not None:
         dpt_hip.set_ycache_bits(ybits)
     if nomemo:

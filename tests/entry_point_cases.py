@@ -233,7 +233,6 @@ def _add_bandit_cases():
     tile = lambda t: (dpt_hip.set_decode_tile, t, 8)  # noqa: E731
     variants = [("base", [], False, False), ("own-kv", [], False, True), ("ycache32", [bits(32)], False, True),
                 ("tile16", [tile(16)], False, True), ("tile16-ycache32", [tile(16), bits(32)], False, False),
-                ("block0-mfma", [(dpt_hip.set_block0_mfma, True, False)], False, True),
                 ("budget0", [(dpt_hip.set_cache_budget, 0, 224 << 20)], False, True),
                 ("bernoulli", [], True, True)]
     for name, tuning, bern, own in variants:

@@ -120,3 +120,18 @@ def test_header_constants_match_binding():
         py = getattr(_lib, "DPT_" + name, getattr(_lib, name, None))
         assert py is not None, name
         assert int(py) == int(val), (name, py, val)
+
+
+def test_block0_mfma_key_is_retired():
+    """DPT_TUNE_BLOCK0_MFMA keeps its number; 0 (the vector path, the only form left) is accepted,
+    any other value is refused with an error that names the key."""
+    from dpt_hip import _lib
+    lib = _lib.load()
+    _lib.call("dpt_tuning_set", _lib.TUNE_BLOCK0_MFMA, 0)
+    with pytest.raises(NotImplementedError):
+        _lib.call("dpt_tuning_set", _lib.TUNE_BLOCK0_MFMA, 1)
+    assert b"BLOCK0_MFMA" in lib.dpt_last_error()
+    import dpt_hip
+    dpt_hip.set_block0_mfma(False)  # the Python setter stays for callers written for the knob
+    with pytest.raises(NotImplementedError):
+        dpt_hip.set_block0_mfma(True)

@@ -43,33 +43,27 @@ def param_lds(F, L, A):
     return (F * E + E + L * 416 + 2 * E + E * A + A + 3) & ~3
 
 
-def rollout_lds(A, L, with_G, l0m=False):
+def rollout_lds(A, L, with_G):
     """dpt_decode.hip RolloutLDS: means double [16][A], base [(A + 1)][32], g0 and bvp [L][32], Wvp
-    [L][32][32], G [L][32][32] when kept in LDS, and l0_tiles' gx [32][C] + gx0 [C] (C = 16 for
-    A + 3 <= 16, else 32) for block 0 on the matrix cores."""
-    n = 2 * M_ROWS * A + (A + 1) * E + 2 * L * E + L * E * E + (L * E * E if with_G else 0)
-    if l0m:
-        cols = 16 if A + 3 <= 16 else 32
-        n += E * cols + cols
-    return n
+    [L][32][32], and G [L][32][32] when kept in LDS."""
+    return 2 * M_ROWS * A + (A + 1) * E + 2 * L * E + L * E * E + (L * E * E if with_G else 0)
 
 
-def rollout_bytes(L, A, with_G, l0m=False):
-    return 4 * (SMEM + param_lds(A + 3, L, A) + rollout_lds(A, L, with_G, l0m))
+def rollout_bytes(L, A, with_G):
+    return 4 * (SMEM + param_lds(A + 3, L, A) + rollout_lds(A, L, with_G))
 
 
-def rollout_instantiation(L, A, tile, block0_mfma=False):
-    """launch_rollout_bandit's choice: (TILE, GL, L0M), or None where it rejects the model.  G stays
+def rollout_instantiation(L, A, tile):
+    """launch_rollout_bandit's choice: (TILE, GL), or None where it rejects the model.  G stays
     in LDS (GL) while the block still lets the tile's workgroups share a CU: 80 KiB at tile 8 (two
     workgroups), 160 KiB at tile 16 (one).  With A = 5 (F = 8) the block is 38,560 + 10,112 L bytes
     with G and 38,560 + 6,016 L without, so tile 8 keeps G for L <= 4, tile 16 for L <= 12, and the
     rollout is rejected from L = 21 on (164,896 B > 163,840).  With A = 20: 46,288 + 10,112 L, so
     tile 8 keeps G for L <= 3."""
-    l0m = block0_mfma and tile == 8 and A == 5
-    gl = rollout_bytes(L, A, True, l0m) <= LDS // (2 if tile == 8 else 1)
-    if rollout_bytes(L, A, gl, l0m) > LDS:
+    gl = rollout_bytes(L, A, True) <= LDS // (2 if tile == 8 else 1)
+    if rollout_bytes(L, A, gl) > LDS:
         return None
-    return tile, gl, 6 if l0m else 0
+    return tile, gl
 
 
 def prefill_dyn_bytes(L, F, A):
@@ -99,7 +93,7 @@ def test_layout_arithmetic():
     assert [rollout_instantiation(L, 5, 16)[1] for L in (12, 13)] == [True, False]
     assert [rollout_instantiation(L, 20, 8)[1] for L in (3, 4)] == [True, False]
     assert rollout_bytes(20, 5, False) == 158880 and rollout_bytes(21, 5, False) == 164896
-    assert rollout_instantiation(20, 5, 16) == (16, False, 0) and rollout_instantiation(21, 5, 16) is None
+    assert rollout_instantiation(20, 5, 16) == (16, False) and rollout_instantiation(21, 5, 16) is None
     assert rollout_instantiation(21, 5, 8) is None
     assert (kvbuf_bytes(128), kvbuf_bytes(256), kvbuf_bytes(512)) == (35360, 70176, 139808)
     assert [prefill_window(L, 8, 5) for L in (15, 16, 64)] == [512, 256, 256]
@@ -330,31 +324,29 @@ def test_forward_bar_tells_a_perturbed_model():
 
 N_ROLL, H_ROLL, VAR_ROLL, SEED_ROLL = 19, 70, 0.3, 2718  # 3 tiles of 8 (last: 3 live) / 2 of 16; H crosses the 64-position y chunk
 
-# (L, A, tile, block-0 MFMA, GL expected, what it pins)
+# (L, A, tile, GL expected, what it pins)
 ROLLOUT_CASES = [
-    (1, 5, 8, False, True, "single block: no y cache, rollout_pin nb = 0, last on block 0"),
-    (1, 32, 8, False, True, "single block, both head tiles full"),
-    (1, 1, 8, False, True, "single block, one arm"),
-    (2, 5, 8, False, True, "one cached block"),
-    (3, 5, 8, False, True, "two cached blocks"),
-    (5, 5, 8, False, False, "<8,false> with the A = 5 register select"),
-    (6, 5, 8, False, False, "<8,false> with the A = 5 register select"),
-    (3, 20, 8, False, True, "<8,true> with the A = 20 register select"),
-    (4, 2, 8, False, True, "select_from_logits, GL on"),
-    (4, 3, 8, False, True, "select_from_logits, GL on"),
-    (3, 11, 8, False, True, "select_from_logits, GL on (at L = 4 eleven arms already put G out of LDS)"),
-    (5, 2, 8, False, False, "select_from_logits, GL off"),
-    (4, 16, 8, False, False, "one full head tile, wave-local hand-off"),
-    (4, 17, 8, False, False, "second head tile with one live column, barrier path"),
-    (2, 17, 8, False, True, "the same with G in LDS"),
-    (4, 32, 8, False, False, "both head tiles full"),
-    (4, 11, 16, False, True, "<16,true> with the generic select"),
-    (13, 5, 16, False, False, "<16,false>"),
-    (20, 5, 16, False, False, "<16,false>, the deepest accepted model"),
-    (4, 5, 8, True, True, "<8,true,6>: block 0 on the matrix cores against the oracle directly"),
-    (3, 5, 8, True, True, "<8,true,6> at another depth"),
+    (1, 5, 8, True, "single block: no y cache, rollout_pin nb = 0, last on block 0"),
+    (1, 32, 8, True, "single block, both head tiles full"),
+    (1, 1, 8, True, "single block, one arm"),
+    (2, 5, 8, True, "one cached block"),
+    (3, 5, 8, True, "two cached blocks"),
+    (5, 5, 8, False, "<8,false> with the A = 5 register select"),
+    (6, 5, 8, False, "<8,false> with the A = 5 register select"),
+    (3, 20, 8, True, "<8,true> with the A = 20 register select"),
+    (4, 2, 8, True, "select_from_logits, GL on"),
+    (4, 3, 8, True, "select_from_logits, GL on"),
+    (3, 11, 8, True, "select_from_logits, GL on (at L = 4 eleven arms already put G out of LDS)"),
+    (5, 2, 8, False, "select_from_logits, GL off"),
+    (4, 16, 8, False, "one full head tile, wave-local hand-off"),
+    (4, 17, 8, False, "second head tile with one live column, barrier path"),
+    (2, 17, 8, True, "the same with G in LDS"),
+    (4, 32, 8, False, "both head tiles full"),
+    (4, 11, 16, True, "<16,true> with the generic select"),
+    (13, 5, 16, False, "<16,false>"),
+    (20, 5, 16, False, "<16,false>, the deepest accepted model"),
 ]
-_ROLL_ID = lambda c: "L%d-A%d-tile%d%s" % (c[0], c[1], c[2], "-l0m" if c[3] else "")  # noqa: E731
+_ROLL_ID = lambda c: "L%d-A%d-tile%d" % (c[0], c[1], c[2])  # noqa: E731
 
 
 def bandit_draws(d, N, H, seed, bernoulli=False):
@@ -438,7 +430,7 @@ def compare_rollout(out, ref, means, L, label, min_share=0.9, err32=0.0):
     return share
 
 
-def run_bandit_case(L, A, tile, l0m, sample=True, bernoulli=False, H=H_ROLL, label=""):
+def run_bandit_case(L, A, tile, sample=True, bernoulli=False, H=H_ROLL, label=""):
     import dpt_hip
     d = K.dh()
     w, W, blob, m = model(L, 1, A, H)
@@ -447,13 +439,11 @@ def run_bandit_case(L, A, tile, l0m, sample=True, bernoulli=False, H=H_ROLL, lab
     u, g = bandit_draws(d, N_ROLL, H, SEED_ROLL, bernoulli)
     try:
         dpt_hip.set_decode_tile(tile)
-        dpt_hip.set_block0_mfma(l0m)
         out = m.rollout_bandit(means, H, var, sample, bandit_type=d.BANDIT_BERNOULLI if bernoulli else
                                d.BANDIT_GAUSSIAN, seed=SEED_ROLL, want_logits=True)
         out = {k: v.clone() for k, v in out.items() if k != "_keep"}
     finally:
-        dpt_hip.set_decode_tile(8)  # the library defaults
-        dpt_hip.set_block0_mfma(False)
+        dpt_hip.set_decode_tile(8)  # the library default
     ref = bandit_reference(L, A, H, W, blob, means, var, u, g, sample, bernoulli)
     ref["err32"] = rollout_fp32_error(W, ref) if L > 8 else 0.0  # only the deeper models' bar needs it
     return out, ref, means
@@ -466,25 +456,25 @@ def test_rollout_bandit_over_layers_and_arms(case):
     named in ROLLOUT_CASES.  Each case first asserts, from the LDS layout (rollout_instantiation),
     that it takes the instantiation it is listed for.  One arm has no cdf edge: every task-step
     must compare."""
-    L, A, tile, l0m, gl, what = case
-    assert rollout_instantiation(L, A, tile, l0m) == (tile, gl, 6 if l0m else 0), what
+    L, A, tile, gl, what = case
+    assert rollout_instantiation(L, A, tile) == (tile, gl), what
     # A = 5 and 20 take select_rollout's register paths, every other count select_from_logits
-    out, ref, means = run_bandit_case(L, A, tile, l0m)
-    compare_rollout(out, ref, means, L, f"L={L} A={A} tile={tile} GL={int(gl)} L0M={6 if l0m else 0}",
+    out, ref, means = run_bandit_case(L, A, tile)
+    compare_rollout(out, ref, means, L, f"L={L} A={A} tile={tile} GL={int(gl)}",
                     min_share=1.0 if A == 1 else 0.9, err32=ref["err32"])
 
 
 def test_rollout_bandit_greedy_five_layers():
     """Greedy selection on <8,false> (L = 5): the first argmax of the logits, no draws."""
-    assert rollout_instantiation(5, 5, 8) == (8, False, 0)
-    out, ref, means = run_bandit_case(5, 5, 8, False, sample=False)
+    assert rollout_instantiation(5, 5, 8) == (8, False)
+    out, ref, means = run_bandit_case(5, 5, 8, sample=False)
     compare_rollout(out, ref, means, 5, "greedy L=5 A=5 tile=8")
 
 
 def test_rollout_bandit_bernoulli_two_tiles_head():
     """Bernoulli rewards (r = u < mean) at L = 2, A = 17 (two head tiles) against the numpy float64
     oracle: rewards are 0 or 1 and equal the oracle's on the compared steps."""
-    out, ref, means = run_bandit_case(2, 17, 8, False, bernoulli=True)
+    out, ref, means = run_bandit_case(2, 17, 8, bernoulli=True)
     assert set(np.unique(out["rewards"].cpu().numpy())) <= {0.0, 1.0}
     compare_rollout(out, ref, means, 2, "bernoulli L=2 A=17 tile=8")
 
@@ -497,7 +487,7 @@ def test_rollout_bar_tells_a_perturbed_model():
     import dpt_hip
     from oracle import c_oracle
     L, A, H = 2, 5, H_ROLL
-    out, ref, means = run_bandit_case(L, A, 8, False)
+    out, ref, means = run_bandit_case(L, A, 8)
     compare_rollout(out, ref, means, L, "L=2 A=5 tile=8 (true weights)")
     w = model(L, 1, A, H)[0]
     d = K.dh()
@@ -523,7 +513,7 @@ def test_rollout_rejected_by_lds_leaves_the_model_usable():
     assert max(L for L in range(1, 65) if rollout_instantiation(L, 5, 8)) == 20
     assert max(L for L in range(1, 65) if rollout_instantiation(L, 5, 16)) == 20
     H = 24
-    out, ref, means = run_bandit_case(20, 5, 8, False, H=H)
+    out, ref, means = run_bandit_case(20, 5, 8, H=H)
     compare_rollout(out, ref, means, 20, "L=20 A=5 tile=8 (the limit)", err32=ref["err32"])
     _, _, _, m4 = model(4, 1, 5, H)
     before = m4.rollout_bandit(means, H, VAR_ROLL, True, seed=5, want_logits=True)

@@ -42,7 +42,6 @@ def _defaults():
     import dpt_hip
     dpt_hip.set_decode_tile(8)
     dpt_hip.set_ycache_bits(24)
-    dpt_hip.set_block0_mfma(False)
     dpt_hip.set_prefill(True)
     dpt_hip.set_darkroom_workspace(True)
     dpt_hip.set_darkroom_memo(True)
@@ -148,9 +147,8 @@ def _fp32_rollout_error(r32, r64):
 @pytest.mark.parametrize("tile,N", SM.ROLLOUT_TILES)
 def test_bandit_rollout(tile, N, L, A, level, head):
     """dpt_rollout_bandit against c_oracle.bandit_rollout_f64 on injected draws: H = 9, 70, 130,
-    sampled and greedy, the 24-bit and the fp32 y cache, block 0 on the vector ALUs and (5 arms at tile
-    8, where that path exists) on the matrix cores; the two cache forms within the bar of each other on
-    the steps both followed the oracle.  ``head`` 4: the peaked-head variant, on the project's bar."""
+    sampled and greedy, the 24-bit and the fp32 y cache; the two cache forms within the bar of each other
+    on the steps both followed the oracle.  ``head`` 4: the peaked-head variant, on the project's bar."""
     from test_gpu_ycache_packed import _logit_diff
     d = dh()
     w = SM.rollout_weights(L, A, level, head)
@@ -167,21 +165,19 @@ def test_bandit_rollout(tile, N, L, A, level, head):
             err32 = _fp32_rollout_error(r32, r64)
             bar = SM.bar(level, LOGIT_BAR, err32)
             worst["fp32"] = max(worst["fp32"], err32)
-            for mfma in ((False, True) if tile == 8 and A == 5 else (False,)):
-                d.set_block0_mfma(mfma)
-                outs, n_cmp = {}, {}
-                for bits in (24, 32):
-                    d.set_ycache_bits(bits)
-                    print(f"tile {tile} N {N} L {L} A {A} {level} head x{head:g} H {H} sample {int(sample)} "
-                          f"mfma {int(mfma)} bits {bits} (fp32 oracle {err32:.3e}, bar {bar:.1e}):")
-                    outs[bits] = _run_bandit(m, L, A, N, H, sample)
-                    err, n_cmp[bits], frac = SM.rollout_compare(outs[bits], r64, r64["margin"], bar)
-                    worst[bits] = max(worst[bits], err)
-                    worst["frac"] = min(worst["frac"], frac)
-                diff = _logit_diff(outs[24], outs[32], np.minimum(n_cmp[24], n_cmp[32]))
-                print(f"  24 vs 32: max rel logit diff {diff:.3e}")
-                assert diff <= bar, (diff, bar)
-                worst["24v32"] = max(worst["24v32"], diff)
+            outs, n_cmp = {}, {}
+            for bits in (24, 32):
+                d.set_ycache_bits(bits)
+                print(f"tile {tile} N {N} L {L} A {A} {level} head x{head:g} H {H} sample {int(sample)} "
+                      f"bits {bits} (fp32 oracle {err32:.3e}, bar {bar:.1e}):")
+                outs[bits] = _run_bandit(m, L, A, N, H, sample)
+                err, n_cmp[bits], frac = SM.rollout_compare(outs[bits], r64, r64["margin"], bar)
+                worst[bits] = max(worst[bits], err)
+                worst["frac"] = min(worst["frac"], frac)
+            diff = _logit_diff(outs[24], outs[32], np.minimum(n_cmp[24], n_cmp[32]))
+            print(f"  24 vs 32: max rel logit diff {diff:.3e}")
+            assert diff <= bar, (diff, bar)
+            worst["24v32"] = max(worst["24v32"], diff)
     print(f"SHARP-ERR item=2 rollout tile={tile} N={N} L={L} A={A} {level} head x{head:g}: kernel 24-bit "
           f"{worst[24]:.3e}, 32-bit {worst[32]:.3e}, 24 vs 32 {worst['24v32']:.3e}, fp32 oracle {worst['fp32']:.3e}, "
           f"compared >= {worst['frac']:.4f}")

@@ -3,7 +3,7 @@
 
 - rollout_darkroom_kernel<true, 4, true> (config 3): no scratch and at most 168 VGPRs, so three
   4-wave workgroups share a CU (DESIGN.md §3, DarkRoom);
-- rollout_bandit_kernel<8, *, 0> (config 2, the default vector form of block 0): no scratch and
+- rollout_bandit_kernel<8, *> (config 2): no scratch and
   four waves per SIMD."""
 import os
 import re
@@ -44,7 +44,7 @@ def test_darkroom_config3_kernel_budget(tmp_path):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_bandit_config2_kernel_budget(tmp_path):
     r = remarks("dpt_decode.hip", tmp_path)
-    k = [v for n, v in r.items() if re.search(r"rollout_bandit_kernelILi8ELb[01]ELi0E", n)]
+    k = [v for n, v in r.items() if re.search(r"rollout_bandit_kernelILi8ELb[01]EEE", n)]
     assert len(k) == 2, list(r)
     for v in k:
         assert v["scratch"] == 0 and v["occ"] >= 4, v
