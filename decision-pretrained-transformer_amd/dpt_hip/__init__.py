@@ -636,6 +636,139 @@ def empirical_recommend(actions, rewards, means):
     return out
 
 
+# ----------------------------------------------------------------------------- Bayes posterior of the optimal action
+
+def _bandit_type_code(bandit_type):
+    code = {"uniform": BANDIT_GAUSSIAN, "gaussian": BANDIT_GAUSSIAN, "bernoulli": BANDIT_BERNOULLI}.get(
+        bandit_type, bandit_type)
+    if code not in (BANDIT_GAUSSIAN, BANDIT_BERNOULLI):
+        raise NotImplementedError(f"bandit type {bandit_type!r}: BANDIT_GAUSSIAN or BANDIT_BERNOULLI")
+    return int(code)
+
+
+def posterior_grid(var, H, bandit_type=BANDIT_GAUSSIAN):
+    """The default grid size G of ``bandit_posterior`` for records of H pulls: the smallest power of two
+    >= 8 sqrt(H) / var (Gaussian rewards of std ``var``: the posterior of a mean pulled H times has std
+    var / sqrt(H), so eight grid points per posterior std) or >= 8 H (Bernoulli: a Beta posterior at an end of
+    [0, 1] is as narrow as 1 / H), at least 256.  Above the kernel's 8192 the grid would under-resolve the
+    posterior: ValueError (an explicit ``grid=`` of ``bandit_posterior`` overrides this rule).  No device work."""
+    H, code = int(H), _bandit_type_code(bandit_type)
+    if H < 0:
+        raise ValueError(f"posterior_grid: H={H}")
+    if code == BANDIT_GAUSSIAN:
+        if not float(var) > 0:
+            raise ValueError(f"posterior_grid: Gaussian var={var} (the noise std) is not > 0")
+        need = 8.0 * float(np.sqrt(H)) / float(var)
+    else:
+        need = 8.0 * H
+    G = 256
+    while G < need:
+        G *= 2
+    if G > _lib.POSTERIOR_MAX_GRID:
+        raise ValueError(f"posterior_grid: H={H}" + (f", var={var}" if code == BANDIT_GAUSSIAN else ", Bernoulli") +
+                         f" needs a grid of {G} points, above the kernel's {_lib.POSTERIOR_MAX_GRID}: the posterior "
+                         f"of a much-pulled arm would be under-resolved (narrower than the grid spacing); pass a "
+                         f"shorter record, or an explicit grid= to accept the error")
+    return G
+
+
+def bandit_posterior(actions, rewards, A, var, bandit_type=BANDIT_GAUSSIAN, grid=None, chunk=0):
+    """dpt_bandit_posterior: the grid posterior of the optimal arm (prior means ~ U[0,1]^A, reward std
+    ``var``) after every prefix of the records actions (N, H) int32 / rewards (N, H) -> post (N, H + 1, A)
+    float64 on the device, row t given the first t pulls.  ``grid``: the grid size G (default
+    ``posterior_grid(var, H, bandit_type)``); ``chunk``: tasks per launch (0: all at once); a task's rows do
+    not depend on it.  No host synchronisation; runs on the current stream."""
+    dev = device()
+    acts, rews = _dev(actions, torch.int32, dev), _dev(rewards, torch.float64, dev)
+    if acts.dim() != 2 or acts.shape != rews.shape or acts.shape[0] < 1:
+        raise ValueError(f"actions {tuple(acts.shape)} / rewards {tuple(rews.shape)} are not (N >= 1, H) each")
+    if int(chunk) < 0:
+        raise ValueError(f"bandit_posterior: chunk={chunk}")
+    N, H = (int(x) for x in acts.shape)
+    A, code = int(A), _bandit_type_code(bandit_type)
+    G = posterior_grid(var, H, code) if grid is None else int(grid)
+    step = N if int(chunk) == 0 else min(N, int(chunk))
+    need = ctypes.c_int64()
+    _lib.call("dpt_bandit_posterior_workspace_numel", step, A, G, ctypes.byref(need))
+    ws = torch.empty(need.value, dtype=torch.float64, device=dev)
+    post = torch.empty((N, H + 1, A), dtype=torch.float64, device=dev)
+    for off in range(0, N, step):
+        n = min(step, N - off)
+        args = _lib.BanditPosteriorArgs(n, H, A, code, G, 0, float(var), acts[off:].data_ptr() if H else None,
+                                        rews[off:].data_ptr() if H else None, ws.data_ptr(), post[off:].data_ptr())
+        _lib.call("dpt_bandit_posterior", ctypes.byref(args), _stream())
+    for t in (acts, rews, ws):  # the launches are asynchronous: the caching allocator must not hand these
+        t.record_stream(torch.cuda.current_stream())  # blocks to another stream before they ran
+    return post
+
+
+def darkroom_posterior(goals, query, next_states, rewards, dim, want_consistent=False):
+    """dpt_darkroom_posterior: the posterior of the expert action at ``query`` (N, 2) after every prefix of
+    the transitions next_states (N, H, 2) / rewards (N, H), the goal uniform over the rows of ``goals``
+    (n_goals, 2) (with multiplicity; identity action permutation) -> post (N, H + 1, 5) float64, and with
+    ``want_consistent`` (post, consistent (N, H + 1) int32: how many goals the prefix leaves).  No host
+    synchronisation; runs on the current stream."""
+    dev = device()
+    gl = _dev(goals, torch.int32, dev).reshape(-1, 2)
+    q = _dev(query, torch.int32, dev)
+    ns, rw = _dev(next_states, torch.int32, dev), _dev(rewards, torch.int32, dev)
+    if q.dim() != 2 or q.shape[1] != 2 or q.shape[0] < 1 or rw.dim() != 2 or rw.shape[0] != q.shape[0] or \
+            tuple(ns.shape) != tuple(rw.shape) + (2,):
+        raise ValueError(f"query {tuple(q.shape)} / next_states {tuple(ns.shape)} / rewards {tuple(rw.shape)} are "
+                         f"not (N >= 1, 2) / (N, H, 2) / (N, H)")
+    N, H = (int(x) for x in rw.shape)
+    post = torch.empty((N, H + 1, 5), dtype=torch.float64, device=dev)
+    cons = torch.empty((N, H + 1), dtype=torch.int32, device=dev) if want_consistent else None
+    args = _lib.DarkroomPosteriorArgs(N, H, int(dim), int(gl.shape[0]), 0, 0, gl.data_ptr(), q.data_ptr(),
+                                      ns.data_ptr() if H else None, rw.data_ptr() if H else None, post.data_ptr(),
+                                      None if cons is None else cons.data_ptr())
+    _lib.call("dpt_darkroom_posterior", ctypes.byref(args), _stream())
+    for t in (gl, q, ns, rw):
+        t.record_stream(torch.cuda.current_stream())
+    return (post, cons) if want_consistent else post
+
+
+def posterior_compare(post, logits, targets):
+    """dpt_posterior_compare: post (N, T, A) float64 against a model's logits (N, T, A) float32 for the
+    optimal actions targets (N) -> dict of (N, T) float64 device tensors nll_model, nll_bayes, kl, entropy
+    (all arithmetic in float64).  No host synchronisation; runs on the current stream."""
+    dev = device()
+    ps, lg = _dev(post, torch.float64, dev), _dev(logits, torch.float32, dev)
+    tg = _dev(targets, torch.int64, dev).reshape(-1)
+    if ps.dim() != 3 or ps.shape != lg.shape or ps.shape[0] < 1 or tg.numel() != ps.shape[0]:
+        raise ValueError(f"post {tuple(ps.shape)} / logits {tuple(lg.shape)} / targets {tg.numel()} are not "
+                         f"(N >= 1, T, A) / (N, T, A) / N")
+    N, T, A = (int(x) for x in ps.shape)
+    out = {k: torch.empty((N, T), dtype=torch.float64, device=dev) for k in ("nll_model", "nll_bayes", "kl", "entropy")}
+    args = _lib.PosteriorCompareArgs(N, T, A, 0, ps.data_ptr(), lg.data_ptr(), tg.data_ptr(),
+                                     *(out[k].data_ptr() for k in ("nll_model", "nll_bayes", "kl", "entropy")))
+    _lib.call("dpt_posterior_compare", ctypes.byref(args), _stream())
+    for t in (ps, lg, tg):
+        t.record_stream(torch.cuda.current_stream())
+    return out
+
+
+def fresh_posterior(env, batch, grid=None, chunk=0):
+    """The Bayes posterior of the optimal action on every prefix of the fresh-task generator's samples
+    ``batch`` (``fresh_batch(env, ...)`` with its outputs): (post (n, 1 + H, A) float64, targets (n) int64).
+    The records are read back from the tokens, so the posterior is given exactly the context the model is
+    given (the rewards as the float32 the tokens hold).  The prior is ``env``'s own: U[0,1]^A means with
+    reward std ``env.var`` for a bandit, ``env.goals`` for DarkRoom.  The linear bandit (no cheap P(arm
+    optimal)) and DarkRoom with a permutation list (the permutation is latent too) are not covered."""
+    if env.kind == FreshEnv.LINEAR:
+        raise NotImplementedError("the linear bandit's posterior over theta is Gaussian, but the probability that "
+                                  "an arm is optimal is a lin_d-dimensional integral: no Bayes posterior here")
+    tok, tg = batch["tokens"], batch["opt_action"].to(torch.int64)
+    if env.kind == _lib.FRESH_BANDIT:
+        A = env.action_dim
+        acts = tok[:, 1:, 1:1 + A].argmax(dim=-1).to(torch.int32)
+        return bandit_posterior(acts, tok[:, 1:, 2 + A].to(torch.float64), A, env.var, env.type, grid, chunk), tg
+    if env.perms is not None:
+        raise NotImplementedError("DarkRoom with an action-permutation list: the permutation is latent too")
+    return darkroom_posterior(env.goals, tok[:, 0, :2].to(torch.int32), tok[:, 1:, 7:9].to(torch.int32),
+                              tok[:, 1:, 9].to(torch.int32), env.dim), tg
+
+
 def set_decode_tile(tile):
     """Tasks per workgroup of the decode kernels (8: two workgroups per CU; 16: one)."""
     _lib.call("dpt_tuning_set", _lib.TUNE_DECODE_TILE, int(tile))

@@ -370,6 +370,35 @@ SIGNATURES["dpt_exploit_eval_workspace_numel"] = (_i32, [_train_desc_p, _i32, _i
 SIGNATURES["dpt_exploit_eval"] = (_i32, [_train_desc_p, _c_void_p, ctypes.POINTER(ExploitEvalArgs), _c_void_p])
 
 
+POSTERIOR_MIN_GRID, POSTERIOR_MAX_GRID = 64, 8192  # dpt_bandit_posterior_args.G: a multiple of 64 in this range
+
+
+class BanditPosteriorArgs(ctypes.Structure):
+    """dpt_bandit_posterior_args: the grid posterior of the optimal arm on every prefix of N records."""
+    _fields_ = [("N", _i32), ("H", _i32), ("A", _i32), ("type", _i32), ("G", _i32), ("flags", _i32), ("var", _f64),
+                ("actions", _c_void_p), ("rewards", _c_void_p), ("workspace", _c_void_p), ("post", _c_void_p)]
+
+
+class DarkroomPosteriorArgs(ctypes.Structure):
+    """dpt_darkroom_posterior_args: the posterior of the expert action on every prefix of N DarkRoom samples."""
+    _fields_ = [("N", _i32), ("H", _i32), ("dim", _i32), ("n_goals", _i32), ("flags", _i32), ("reserved", _i32),
+                ("goals", _c_void_p), ("query", _c_void_p), ("next_states", _c_void_p), ("rewards", _c_void_p),
+                ("post", _c_void_p), ("consistent", _c_void_p)]
+
+
+class PosteriorCompareArgs(ctypes.Structure):
+    """dpt_posterior_compare_args: a posterior against a model's logits, row by row."""
+    _fields_ = [("N", _i32), ("T", _i32), ("A", _i32), ("flags", _i32), ("post", _c_void_p), ("logits", _c_void_p),
+                ("targets", _c_void_p), ("nll_model", _c_void_p), ("nll_bayes", _c_void_p), ("kl", _c_void_p),
+                ("entropy", _c_void_p)]
+
+
+SIGNATURES["dpt_bandit_posterior_workspace_numel"] = (_i32, [_i32, _i32, _i32, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_bandit_posterior"] = (_i32, [ctypes.POINTER(BanditPosteriorArgs), _c_void_p])
+SIGNATURES["dpt_darkroom_posterior"] = (_i32, [ctypes.POINTER(DarkroomPosteriorArgs), _c_void_p])
+SIGNATURES["dpt_posterior_compare"] = (_i32, [ctypes.POINTER(PosteriorCompareArgs), _c_void_p])
+
+
 SITE_IMAGE_ENC = 1 << 20  # Philox site of the image encoder's dropout (DPT_SITE_IMAGE_ENC)
 
 

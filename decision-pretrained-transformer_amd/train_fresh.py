@@ -20,6 +20,14 @@ data types; it collects 'thompson').  The two are different training distributio
 (equal to collect_data.py's in law, not bit for bit: the tasks are other draws), 'uniform' the bandit's i.i.d.
 behaviour policy.  The arms are collect_data.py's (``RandomState(1234)``, ``--dim`` x ``--lin_d``), the file
 names and the extra checkpoint every 10 epochs are train.py's, and ``--shuffle`` is refused as train.py refuses it.
+
+``--bayes_floor`` (bandit, bandit_thompson, darkroom*): before epoch 1, the irreducible floor of the printed
+test loss, ``E[-log P(a* | D_t)]`` averaged over t = 1 .. H of the test samples (the same every epoch) under
+the exact Bayes posterior of the optimal action (dpt_hip.fresh_posterior; the DarkRoom prior is the list the
+test samples are drawn from), printed and logged as one line ``\tBayes floor (test): ...``.  The test loss
+minus this floor is the mean KL from the posterior to the model.  Refused for linear_bandit: P(arm optimal)
+under its Gaussian posterior over theta is a lin_d-dimensional integral with no cheap form.  Without the flag
+the log and every file are as before.
 """
 import argparse
 import hashlib
@@ -30,7 +38,7 @@ import numpy as np
 import torch
 
 import common_args
-from dpt_hip import FreshEnv
+from dpt_hip import FreshEnv, fresh_batch, fresh_posterior, posterior_compare, posterior_grid
 from dpt_hip.train import FreshTrainer
 from models.net import Transformer
 from train_common import LossLog, set_seeds
@@ -55,6 +63,21 @@ def darkroom_goals(env, dim):
     return goals[:split], goals[split:]
 
 
+FLOOR_CHUNK = 2048  # test samples per posterior launch (post is (chunk, 1 + H, A) float64)
+
+
+def bayes_floor(test_env, test_key, n_test, horizon):
+    """sum_{t=1..H} -log P(a* | D_t) / H / n_test over the test samples 0 .. n_test - 1 of ``test_key``: the
+    floor of the test loss main() prints (one host read at the end)."""
+    total = torch.zeros((), dtype=torch.float64, device=device)
+    for lo in range(0, n_test, FLOOR_CHUNK):
+        batch = fresh_batch(test_env, test_key, lo, min(FLOOR_CHUNK, n_test - lo))
+        post, targets = fresh_posterior(test_env, batch)
+        nll = posterior_compare(post, torch.zeros(post.shape, dtype=torch.float32, device=post.device), targets)
+        total += nll["nll_bayes"][:, 1:].sum()
+    return float(total.item()) / horizon / max(n_test, 1)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser()
     common_args.add_dataset_args(parser)
@@ -64,6 +87,8 @@ def main(argv=None):
     parser.add_argument("--batch", type=int, default=64)
     parser.add_argument("--data_type", choices=["thompson", "uniform"], default=None,
                         help="linear_bandit only: the rollin, collect_data.py's data types")
+    parser.add_argument("--bayes_floor", action="store_true",
+                        help="print the Bayes floor of the test loss before epoch 1 (bandit, bandit_thompson, darkroom*)")
     args = vars(parser.parse_args(argv))
     print("Args: ", args)
 
@@ -83,6 +108,13 @@ def main(argv=None):
         raise ValueError(f"--data_type {data_type} belongs to --env linear_bandit, not to {env}")
     if batch < 1:
         raise ValueError(f"--batch {batch}")
+    if args["bayes_floor"]:
+        if env == "linear_bandit":
+            raise NotImplementedError("--bayes_floor: the linear bandit's posterior over theta is Gaussian, but the "
+                                      "probability that an arm is optimal under it is a lin_d-dimensional integral "
+                                      "with no cheap form; the floor exists for bandit, bandit_thompson and darkroom*")
+        if env in ("bandit", "bandit_thompson"):  # ValueError where the grid would under-resolve the posterior
+            posterior_grid(var, horizon, "uniform" if env == "bandit" else "bernoulli")
 
     os.makedirs("figs/loss", exist_ok=True)
     os.makedirs("trained_models", exist_ok=True)
@@ -126,6 +158,8 @@ def main(argv=None):
     test_loss, train_loss = [], []
     printw("Num train batches: " + str(-(-n_train // batch)))
     printw("Num test batches: " + str(-(-n_test // batch)))
+    if args["bayes_floor"]:
+        printw(f"\tBayes floor (test): {bayes_floor(test_env, test_key, n_test, horizon)}")
 
     for epoch in range(args["num_epochs"]):
         printw(f"Epoch: {epoch + 1}")

@@ -65,7 +65,9 @@ extern "C" {
  * dpt_interactive_mdp_workspace_numel, dpt_interactive_mdp_grad); the in-episode DarkRoom rollout in one
  * launch (dpt_rollout_darkroom_episode); the fresh-task generator and its training step (DPT_STREAM_TASK,
  * dpt_fresh_args, dpt_fresh_batch, dpt_fresh_step, dpt_fresh_eval_loss) and its linear-bandit twin
- * (dpt_fresh_linear_args, dpt_fresh_linear_batch, dpt_fresh_linear_step, dpt_fresh_linear_eval_loss) */
+ * (dpt_fresh_linear_args, dpt_fresh_linear_batch, dpt_fresh_linear_step, dpt_fresh_linear_eval_loss); the
+ * Bayes posterior of the optimal action (dpt_bandit_posterior_workspace_numel, dpt_bandit_posterior,
+ * dpt_darkroom_posterior, dpt_posterior_compare) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -1012,6 +1014,108 @@ int dpt_exploit_eval_workspace_numel(const dpt_train_desc* desc_host, int32_t N,
  * workspace that is not 16-byte aligned. */
 int dpt_exploit_eval(const dpt_train_desc* desc_host, const float* blob, const dpt_exploit_eval_args* args_host,
                      void* stream);
+
+/* ------------------------------------------------------------------ Bayes posterior of the optimal action
+ * The minimiser of the pretraining cross-entropy is the posterior of the optimal action given the context;
+ * for the two task families the fresh-task generator draws from it is computable, and these entry points
+ * compute it for EVERY prefix t = 0 .. H of a context (row t: the first t transitions), where the model's
+ * logits after t transitions already live.  ABI 8, additive.  tests/posterior_oracle.py restates the
+ * definitions in numpy.
+ *
+ * Bandit grid posterior (prior means ~ U[0,1]^A, i.i.d. rollin, `var` the reward std as everywhere here).
+ *   inputs   actions (N, H) int32, rewards (N, H) fp64, A <= 32, type DPT_BANDIT_GAUSSIAN / _BERNOULLI,
+ *            var (Gaussian: > 0), G
+ *   grid     G a multiple of 64 in [64, 8192]; x_i = (i + 0.5) / G
+ *   row t    n_a = the number of pulls j < t with actions[j] == a, s_a = the sum of their rewards IN PULL
+ *            ORDER in fp64; an action outside [0, A) adds to no arm
+ *   log-likelihood, in exactly this operation order (no fused multiply-add):
+ *            Gaussian   l_a(i) = -((n_a * x_i) * x_i - (2 * s_a) * x_i) / ((2 * var) * var)
+ *            Bernoulli  l_a(i) = s_a * log(x_i) + (n_a - s_a) * log1p(-x_i)
+ *   weights  w_a(i) = exp(l_a(i) - max_i l_a) / sum_i exp(l_a(i) - max_i l_a)
+ *   mid-point CDF        C_a(i) = sum_{j<i} w_a(j) + w_a(i) / 2
+ *   unnormalised         u_a = sum_i w_a(i) * prod_{b != a} C_b(i)
+ *   output   post[n][t][a] = u_a / sum_b u_b, (N, H + 1, A) fp64; 1 for A == 1
+ * The reduction order is fixed: repeated calls are bit-identical, and a task's rows do not depend on N or
+ * on how the caller chunks the tasks.
+ *
+ * DarkRoom posterior (the goal uniform over a list, reward 1 iff the next state is the goal).
+ *   inputs   goals (n_goals, 2) int32: the prior, with multiplicity; query (N, 2), next_states (N, H, 2),
+ *            rewards (N, H), all int32
+ *   goal k is consistent with the first t transitions iff for every j < t
+ *            (rewards[j] != 0) == (next_states[j] == goals[k])
+ *   post[n][t][a] = #{consistent k whose expert action at the query (identity permutation:
+ *            dpt_darkroom_opt_action with perm NULL) is a} / #{consistent k}, one fp64 division of exact
+ *            integers, (N, H + 1, 5) fp64; a row with no consistent goal is all zeros
+ *   consistent (N, H + 1) int32, optional: the number of consistent k
+ * Action-permutation lists make the permutation latent too and are not covered.
+ *
+ * Compare: post (N, T, A) fp64, logits (N, T, A) fp32, targets (N) int64 in [0, A) (a target outside:
+ * NaN in both nll outputs).  All arithmetic in fp64, logq = log_softmax(logits) with the maximum
+ * subtracted; each output (N, T) fp64 and each may be NULL:
+ *   nll_model = -logq[target]            nll_bayes = -log post[target]   (+inf where it is 0)
+ *   kl        = sum_{a: post_a > 0} post_a (log post_a - logq_a)
+ *   entropy   = -sum_{a: post_a > 0} post_a log post_a
+ * so E[nll_model] - E[nll_bayes] = E[kl] when post is the posterior of the target.                        */
+typedef struct dpt_bandit_posterior_args {
+    int32_t N;                 /* tasks                                                             */
+    int32_t H;                 /* recorded pulls per task (>= 0): rows 0 .. H                       */
+    int32_t A;                 /* arms, <= 32                                                       */
+    int32_t type;              /* DPT_BANDIT_GAUSSIAN / DPT_BANDIT_BERNOULLI                        */
+    int32_t G;                 /* grid points: a multiple of 64 in [64, 8192]                       */
+    int32_t flags;             /* 0                                                                 */
+    double var;                /* reward std (Gaussian: > 0; Bernoulli: ignored)                    */
+    const int32_t* actions;    /* (N, H) (NULL when H = 0)                                          */
+    const double* rewards;     /* (N, H)                                                            */
+    double* workspace;         /* dpt_bandit_posterior_workspace_numel doubles                      */
+    double* post;              /* (N, H + 1, A)                                                     */
+} dpt_bandit_posterior_args;
+
+/* doubles of workspace for N tasks: the grid's log tables (2 G) and, where the 2 A G doubles of a task's
+ * weights and CDFs do not fit in LDS (2 A G 8 B above 128 KiB), one such slot per resident workgroup */
+int dpt_bandit_posterior_workspace_numel(int32_t N, int32_t A, int32_t G, int64_t* numel_out_host);
+/* One launch (two for Bernoulli: the log tables first), no host synchronisation, no allocation.  Host
+ * checks fail before any launch.  DPT_EINVAL: null args / workspace / post, null actions or rewards while
+ * H > 0, N < 1, H < 0, A < 1, a G that is not a multiple of 64 in [64, 8192], a Gaussian var <= 0,
+ * non-zero flags.  DPT_EUNSUPPORTED: A > 32, an unknown type. */
+int dpt_bandit_posterior(const dpt_bandit_posterior_args* args_host, void* stream);
+
+typedef struct dpt_darkroom_posterior_args {
+    int32_t N;                 /* samples                                                           */
+    int32_t H;                 /* transitions per sample (>= 0): rows 0 .. H                        */
+    int32_t dim;               /* room side, <= 255                                                 */
+    int32_t n_goals;           /* rows of goals, 1 .. 2^18                                          */
+    int32_t flags;             /* 0                                                                 */
+    int32_t reserved;          /* 0                                                                 */
+    const int32_t* goals;      /* (n_goals, 2) the prior, with multiplicity                         */
+    const int32_t* query;      /* (N, 2)                                                            */
+    const int32_t* next_states;/* (N, H, 2) (NULL when H = 0)                                       */
+    const int32_t* rewards;    /* (N, H)                                                            */
+    double* post;              /* (N, H + 1, 5)                                                     */
+    int32_t* consistent;       /* (N, H + 1), or NULL                                               */
+} dpt_darkroom_posterior_args;
+
+/* One launch, one wave per sample.  DPT_EINVAL: null args / goals / query / post, null next_states or
+ * rewards while H > 0, N < 1, H < 0, n_goals < 1, dim < 1, non-zero flags / reserved.  DPT_EUNSUPPORTED:
+ * dim > 255, n_goals > 2^18. */
+int dpt_darkroom_posterior(const dpt_darkroom_posterior_args* args_host, void* stream);
+
+typedef struct dpt_posterior_compare_args {
+    int32_t N;                 /* tasks                                                             */
+    int32_t T;                 /* rows per task (>= 1)                                              */
+    int32_t A;                 /* actions, <= 32                                                    */
+    int32_t flags;             /* 0                                                                 */
+    const double* post;        /* (N, T, A)                                                         */
+    const float* logits;       /* (N, T, A)                                                         */
+    const int64_t* targets;    /* (N)                                                               */
+    double* nll_model;         /* (N, T) each, or NULL                                              */
+    double* nll_bayes;
+    double* kl;
+    double* entropy;
+} dpt_posterior_compare_args;
+
+/* One launch, one thread per row.  DPT_EINVAL: null args / post / logits / targets, N < 1, T < 1, A < 1,
+ * non-zero flags.  DPT_EUNSUPPORTED: A > 32. */
+int dpt_posterior_compare(const dpt_posterior_compare_args* args_host, void* stream);
 
 /* ------------------------------------------------------------------ image-conditioned DPT (ImageTransformer)
  * models/net.py:63-132: per token an image (3, 25, 25) goes through Conv2d(3,16,k3,s2) -> ReLU ->
