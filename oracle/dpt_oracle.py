@@ -274,13 +274,14 @@ def bandit_online_rollout(W, means, H, var, u, g, sample=True, dtype=np.float64,
 
 
 def darkroom_online_rollout(W, goals, Heps, H, horizon, u, sample=True, perm=None,
-                            dim=10, dtype=np.float64):
+                            dim=10, dtype=np.float64, temp=1.0):
     """evals/eval_darkroom.py:20-84 ``deploy_online_vec`` with
     DarkroomTransformerController (ctrls/ctrl_darkroom.py:23-66) and
     ``DarkroomEnvVec.deploy_eval`` (envs/darkroom_env.py:151-175).
 
     Episode i < H/horizon sees the first i episodes; later episodes see the last
-    H/horizon episodes (shift-append :75-82).  Returns (N, Heps) returns.
+    H/horizon episodes (shift-append :75-82).  ``temp``: the controller's sampling temperature
+    (ctrl_darkroom.py:51 divides the logits by it; 1.0 there).  Returns (N, Heps) returns.
     """
     goals = np.asarray(goals)
     N = goals.shape[0]
@@ -303,7 +304,7 @@ def darkroom_online_rollout(W, goals, Heps, H, horizon, u, sample=True, perm=Non
             lg = transformer_forward(W, s.astype(np.float64), *b, dtype=dtype).astype(np.float32)
             logs.append(lg)
             a = select_actions(lg, u[ep, t] if sample else None, sample,
-                               temp=1.0 if sample else None)
+                               temp=temp if sample else None)
             ns, r = darkroom_transit(s, a, goals, dim, perm)
             acts.append(a)
             es.append(s.copy())

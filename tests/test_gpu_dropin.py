@@ -320,6 +320,29 @@ def test_eval_darkroom_device_loop_matches_reference(fused):
         assert np.array_equal(ret, r["returns"]), tag
 
 
+def test_eval_darkroom_device_loop_temperature():
+    """controller.temp = 0.5 (ctrls/ctrl_darkroom.py:51 divides the logits by it): the fused rollout, which
+    takes it as dpt_darkroom_rollout_args.temp, gives the returns of the per-step loop, which hands it to
+    dpt_select_action, on the sampled case's goals and draws; and they are not the returns at temp 1."""
+    from ctrls.ctrl_darkroom import DarkroomTransformerController
+    from envs.darkroom_env import DarkroomEnv, DarkroomEnvVec
+    from evals import eval_darkroom
+    _, m = ref_model("darkroom")
+    r = golden("rollout_darkroom_sample.npz")
+    n, Heps, H, horizon, _ = (int(x) for x in r["cfg"])
+    u = r["u"].reshape(-1, n)
+    rets = {}
+    for fused in (True, False):
+        ctrl = DarkroomTransformerController(m, batch_size=n, sample=True)
+        ctrl.temp = 0.5
+        ctrl.uniforms = lambda k: u[k]
+        vec = DarkroomEnvVec([DarkroomEnv(10, g_, horizon) for g_ in r["goals"]])
+        assert eval_darkroom._fused_ok(vec, ctrl, H)
+        rets[fused] = eval_darkroom.deploy_online_vec(vec, ctrl, Heps, H, horizon, fused=fused)
+    assert np.array_equal(rets[True], rets[False])
+    assert not np.array_equal(rets[True], r["returns"])
+
+
 def test_eval_darkroom_per_step_memo_bit_identical():
     """The per-step device loop (fused=False, window 1 + 2*130 = 261) forwards only the tasks
     whose state is new in the episode; returns are identical with the memo off."""

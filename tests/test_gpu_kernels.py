@@ -334,6 +334,47 @@ def test_rollout_darkroom_philox_vs_oracle(Heps, horizon, R):
     assert np.array_equal(out["returns"].cpu().numpy(), ref["returns"])
 
 
+_TEMP_REF = {}
+
+
+@pytest.mark.parametrize("ws", [True, False])
+@pytest.mark.parametrize("memo", [True, False])
+@pytest.mark.parametrize("temp", [0.5, 2.0])
+def test_rollout_darkroom_temperature_vs_oracle(temp, memo, ws):
+    """dpt_darkroom_rollout_args.temp (evals/eval_darkroom.py passes the controller's) at 0.5 and 2 against
+    the oracle sampling at the same temperature, at (3, 30, 2), memo on and off, with and without the
+    workspace: the kernel reads it in finish_step, in the memo chain's fp64 fallback and in the cdf it
+    stores with a memo row.  The project's bar (check_darkroom_tasks): logits within 1e-5 max(1, |x|), a
+    differing action only on a draw within 1e-5 of an edge of the oracle's cdf, >= 0.9 of the task-steps
+    compared."""
+    import dpt_hip
+    _, m, W = model_from_golden("darkroom")
+    N, Heps, horizon, R = 6, 3, 30, 2
+    rs = np.random.RandomState(13)
+    goals = rs.randint(0, 10, (N, 2))
+    u = rs.uniform(size=(Heps * horizon, N))
+    if temp not in _TEMP_REF:  # the oracle depends on neither switch
+        ref = O.darkroom_online_rollout(W, goals, Heps, R * horizon, horizon, u.reshape(Heps, horizon, N), True,
+                                        temp=temp)
+        ref["margin"] = O.boundary_margin(O.softmax_f32(ref["logits"], temp), u)
+        _TEMP_REF[temp] = ref
+    try:
+        dpt_hip.set_darkroom_workspace(ws)
+        dpt_hip.set_darkroom_memo(memo)
+        out = m.rollout_darkroom(goals, Heps, horizon, R, temp=temp, uniforms=u, want_actions=True, want_logits=True,
+                                 want_forwards=True)
+    finally:
+        dpt_hip.set_darkroom_workspace(True)
+        dpt_hip.set_darkroom_memo(True)
+    fw = out["forwards"].cpu().numpy()
+    assert fw.sum() < N * Heps * horizon if memo else (fw == horizon).all()
+    check_darkroom_tasks(out, np.arange(N), _TEMP_REF[temp], Heps, horizon,
+                         label=f"temp {temp} memo {memo} workspace {ws}")
+    # the temperature is read: the same draws at temp 1 take another trajectory
+    base = m.rollout_darkroom(goals, Heps, horizon, R, uniforms=u, want_actions=True)
+    assert not np.array_equal(base["actions"].cpu().numpy(), out["actions"].cpu().numpy())
+
+
 def test_rollout_darkroom_large_properties():
     """Config-3 width (N=4096, window 101) on 2 episodes: deterministic, shard-invariant
     (first_task offsets), returns within [0, horizon]; greedy logits equal the window kernel's."""
