@@ -748,16 +748,82 @@ def posterior_compare(post, logits, targets):
     return out
 
 
+LINEAR_POSTERIOR_GRID = 8192
+
+
+def linear_posterior_grid():
+    """The default number of rays G of ``linear_posterior``: the smallest power of two at which the definition
+    (tests/linear_posterior_oracle.py) stays within 1e-6 of its value at G = 65,536 on every row t >= 1 of the
+    convergence records of tests/test_linear_posterior_host.py (the reference's 10 arms, six tasks of 20 pulls,
+    std 0.3).  Measured worst deviation there: 1.9e-7 at 8,192 (1.9e-6 at 4,096, 1.8e-5 at 2,048: the integrand
+    has kinks where the envelope changes arms, so the rule gains about a factor 10 per doubling, not more)."""
+    return LINEAR_POSTERIOR_GRID
+
+
+def linear_posterior(arms, actions, rewards, var, grid=None, chunk=0):
+    """dpt_linear_posterior: the posterior of the optimal arm of the linear bandit with ``arms`` (A, 2) in the
+    plane (prior theta ~ N(0, I / 2), reward std ``var`` > 0) after every prefix of the records actions (N, H)
+    int32 / rewards (N, H) -> post (N, H + 1, A) float64 on the device, row t given the first t pulls; rows
+    before the first valid pull are the prior in closed form.  ``grid``: the number of rays G (default
+    ``linear_posterior_grid()``); ``chunk``: tasks per launch (0: all at once); a task's rows do not depend on
+    it.  Arms of another width: NotImplementedError.  No host synchronisation; runs on the current stream."""
+    dev = device()
+    x = _dev(arms, torch.float64, dev)
+    acts, rews = _dev(actions, torch.int32, dev), _dev(rewards, torch.float64, dev)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"arms {tuple(x.shape)}: expected (A, 2)")
+    if acts.dim() != 2 or acts.shape != rews.shape or acts.shape[0] < 1:
+        raise ValueError(f"actions {tuple(acts.shape)} / rewards {tuple(rews.shape)} are not (N >= 1, H) each")
+    if int(chunk) < 0:
+        raise ValueError(f"linear_posterior: chunk={chunk}")
+    N, H = (int(v) for v in acts.shape)
+    A, lin_d = (int(v) for v in x.shape)
+    G = linear_posterior_grid() if grid is None else int(grid)
+    step = N if int(chunk) == 0 else min(N, int(chunk))
+    need = ctypes.c_int64()
+    _lib.call("dpt_linear_posterior_workspace_numel", step, A, lin_d, G, ctypes.byref(need))
+    ws = torch.empty(need.value, dtype=torch.float64, device=dev)
+    post = torch.empty((N, H + 1, A), dtype=torch.float64, device=dev)
+    for off in range(0, N, step):
+        n = min(step, N - off)
+        args = _lib.LinearPosteriorArgs(n, H, A, lin_d, G, 0, float(var), x.data_ptr(),
+                                        acts[off:].data_ptr() if H else None, rews[off:].data_ptr() if H else None,
+                                        ws.data_ptr(), post[off:].data_ptr())
+        _lib.call("dpt_linear_posterior", ctypes.byref(args), _stream())
+    for t in (x, acts, rews, ws):
+        t.record_stream(torch.cuda.current_stream())
+    return post
+
+
+def linear_posterior_supported(lin_d, var):
+    """None where ``linear_posterior`` covers a linear bandit of width ``lin_d`` and reward std ``var``, else
+    the reason, a sentence for a NotImplementedError.  No device work."""
+    if int(lin_d) == 2 and float(var) > 0:
+        return None
+    return ("the linear bandit's posterior over theta is Gaussian, but the probability that an arm is optimal "
+            "under it is a lin_d-dimensional integral with no cheap form; supported: lin_d = 2 (a 1-D angular "
+            f"quadrature, dpt_hip.linear_posterior) with a noise std var > 0, not lin_d = {lin_d}, var = {var}")
+
+
 def fresh_posterior(env, batch, grid=None, chunk=0):
     """The Bayes posterior of the optimal action on every prefix of the fresh-task generator's samples
     ``batch`` (``fresh_batch(env, ...)`` with its outputs): (post (n, 1 + H, A) float64, targets (n) int64).
     The records are read back from the tokens, so the posterior is given exactly the context the model is
     given (the rewards as the float32 the tokens hold).  The prior is ``env``'s own: U[0,1]^A means with
-    reward std ``env.var`` for a bandit, ``env.goals`` for DarkRoom.  The linear bandit (no cheap P(arm
-    optimal)) and DarkRoom with a permutation list (the permutation is latent too) are not covered."""
+    reward std ``env.var`` for a bandit, ``env.goals`` for DarkRoom, theta ~ N(0, I / 2) with ``env.arms`` and
+    ``env.var`` for the linear bandit at lin_d = 2 (either rollin: the Thompson rollin depends on theta only
+    through the history, so the likelihood of theta is the same).  The linear bandit at another width or at
+    var = 0 (no cheap P(arm optimal)) and DarkRoom with a permutation list (the permutation is latent too)
+    are not covered."""
     if env.kind == FreshEnv.LINEAR:
-        raise NotImplementedError("the linear bandit's posterior over theta is Gaussian, but the probability that "
-                                  "an arm is optimal is a lin_d-dimensional integral: no Bayes posterior here")
+        why = linear_posterior_supported(env.lin_d, env.var)
+        if why is not None:
+            raise NotImplementedError(why)
+        A = env.action_dim
+        tok = batch["tokens"]
+        acts = tok[:, 1:, 1:1 + A].argmax(dim=-1).to(torch.int32)
+        return (linear_posterior(env.arms, acts, tok[:, 1:, 2 + A].to(torch.float64), env.var, grid, chunk),
+                batch["opt_action"].to(torch.int64))
     tok, tg = batch["tokens"], batch["opt_action"].to(torch.int64)
     if env.kind == _lib.FRESH_BANDIT:
         A = env.action_dim

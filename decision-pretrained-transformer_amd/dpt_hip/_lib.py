@@ -399,6 +399,20 @@ SIGNATURES["dpt_darkroom_posterior"] = (_i32, [ctypes.POINTER(DarkroomPosteriorA
 SIGNATURES["dpt_posterior_compare"] = (_i32, [ctypes.POINTER(PosteriorCompareArgs), _c_void_p])
 
 
+LINEAR_POSTERIOR_MIN_GRID, LINEAR_POSTERIOR_MAX_GRID = 64, 65536  # dpt_linear_posterior_args.G: a multiple of 64
+
+
+class LinearPosteriorArgs(ctypes.Structure):
+    """dpt_linear_posterior_args: the posterior of the optimal arm of the lin_d = 2 linear bandit on every prefix."""
+    _fields_ = [("N", _i32), ("H", _i32), ("A", _i32), ("lin_d", _i32), ("G", _i32), ("flags", _i32), ("var", _f64),
+                ("arms", _c_void_p), ("actions", _c_void_p), ("rewards", _c_void_p), ("workspace", _c_void_p),
+                ("post", _c_void_p)]
+
+
+SIGNATURES["dpt_linear_posterior_workspace_numel"] = (_i32, [_i32, _i32, _i32, _i32, ctypes.POINTER(_i64)])
+SIGNATURES["dpt_linear_posterior"] = (_i32, [ctypes.POINTER(LinearPosteriorArgs), _c_void_p])
+
+
 SITE_IMAGE_ENC = 1 << 20  # Philox site of the image encoder's dropout (DPT_SITE_IMAGE_ENC)
 
 

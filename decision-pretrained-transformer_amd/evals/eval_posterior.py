@@ -1,19 +1,22 @@
 """Is the model's action distribution the Bayes posterior of the optimal action?  Prefix by prefix.
 
 The minimiser of the pretraining cross-entropy is P(a* | D_t), the posterior of the optimal action given the
-first t transitions of the context, and for the bandits and DarkRoom it is computable (dpt_hip.bandit_posterior
-/ dpt_hip.darkroom_posterior; include/dpt_hip.h, "Bayes posterior of the optimal action").  This script puts
+first t transitions of the context, and for the bandits, the linear bandit in the plane and DarkRoom it is
+computable (dpt_hip.bandit_posterior / dpt_hip.linear_posterior / dpt_hip.darkroom_posterior; include/dpt_hip.h,
+"Bayes posterior of the optimal action" and "Linear bandit, lin_d = 2").  This script puts
 a checkpoint's softmax beside it on ``--n_eval`` tasks and reports, per t = 0 .. H as mean +- SEM over the
 tasks: ``kl`` = KL(posterior || model), ``nll_model`` and ``nll_bayes`` (-log of the optimal action's
 probability under each; their gap is the KL in expectation), the posterior's ``entropy`` (which ``nll_bayes``
 equals in expectation), and the optimal action's probability under both.  A regret curve cannot show this.
 
-Flags: evals/eval_interactive_bandit.py's, plus ``--env {bandit,bandit_thompson,darkroom,darkroom_heldout}``
-(bandit_thompson: Bernoulli rewards), ``--context {fresh,online}``, ``--grid`` (the posterior's grid size;
-default dpt_hip.posterior_grid) and ``--chunk`` (tasks per launch).  ``fresh``: the contexts are the fresh-task
+Flags: evals/eval_interactive_bandit.py's, plus ``--env {bandit,bandit_thompson,linear_bandit,darkroom,
+darkroom_heldout}`` (bandit_thompson: Bernoulli rewards; linear_bandit: collect_data.py's arms at ``--lin_d`` 2,
+the generator's rollin chosen by ``--data_type {thompson,uniform}``), ``--context {fresh,online}``, ``--grid``
+(the posterior's grid size; default dpt_hip.posterior_grid, for linear_bandit dpt_hip.linear_posterior_grid) and
+``--chunk`` (tasks per launch).  ``fresh``: the contexts are the fresh-task
 generator's samples under train_fresh.py's test key for ``--seed`` (its held-out goals for darkroom_heldout).
 ``online`` (bandits): the model's own sampled rollout, its records the context -- the distribution the model
-meets when deployed.  The model's row t is one forward over the whole window (the query token sits at position
+meets when deployed (linear_bandit: on ``means = arms @ theta``, theta ~ N(0, I / 2)).  The model's row t is one forward over the whole window (the query token sits at position
 0 and attention is causal): dpt_hip.train.exploit_curve for the bandits, one forward-only every-position
 training forward on the generator's tokens for DarkRoom.  Writes ``<save>/posterior_gap.png`` and
 ``<save>/posterior_gap.json``.
@@ -57,6 +60,25 @@ def bandit_records(model, context, n_eval, dim, horizon, var, bandit_type, seed)
     return out["actions"], out["rewards"], torch.as_tensor(means.argmax(1), device=out["actions"].device)
 
 
+def linear_arms(dim, lin_d):
+    """collect_data.py's arms"""
+    return np.random.RandomState(seed=1234).normal(size=(dim, lin_d)) / np.sqrt(lin_d)
+
+
+def linear_records(model, context, n_eval, arms, horizon, var, data_type, seed):
+    """(actions (n, H) int32, rewards (n, H) float64, targets (n) int64) on the device"""
+    dim = len(arms)
+    if context == "fresh":
+        env = dpt_hip.FreshEnv.linear_bandit(arms, horizon, var, data_type)
+        tok = dpt_hip.fresh_batch(env, generator_key(seed, "test"), 0, n_eval)
+        acts = tok["tokens"][:, 1:, 1:1 + dim].argmax(dim=-1).to(torch.int32)
+        return acts, tok["tokens"][:, 1:, 2 + dim].to(torch.float64), tok["opt_action"].to(torch.int64)
+    theta = np.random.normal(size=(n_eval, arms.shape[1])) / np.sqrt(arms.shape[1])  # sample_linear's prior
+    means = theta @ arms.T
+    out = tr.rollout_bandit_generic(model, means, horizon, var, True, dpt_hip.BANDIT_GAUSSIAN, seed=dpt_hip.next_seed())
+    return out["actions"], out["rewards"], torch.as_tensor(means.argmax(1), device=out["actions"].device)
+
+
 def darkroom_logits(model, tokens, chunk):
     """(n, 1 + H, 5) float32: row t = the model after t transitions (forward-only, every position)"""
     dev = tokens.device
@@ -69,9 +91,19 @@ def darkroom_logits(model, tokens, chunk):
     return torch.cat(out)
 
 
-def run(model, env, context, n_eval, dim, horizon, var, bandit_type, seed, grid=None, chunk=0):
+def run(model, env, context, n_eval, dim, horizon, var, bandit_type, seed, grid=None, chunk=0, lin_d=2,
+        data_type="thompson"):
     """dict key -> (n_eval, H + 1) float64 numpy arrays of KEYS"""
-    if env.startswith("darkroom"):
+    if env == "linear_bandit":
+        why = dpt_hip.linear_posterior_supported(lin_d, var)
+        if why is not None:
+            raise NotImplementedError(why)
+        arms = linear_arms(dim, lin_d)
+        acts, rews, targets = linear_records(model, context, n_eval, arms, horizon, var, data_type, seed)
+        post = dpt_hip.linear_posterior(arms, acts, rews, var, grid, chunk)
+        means = torch.zeros((n_eval, dim), dtype=torch.float64, device=post.device)  # values are not read here
+        logits = tr.exploit_curve(model, acts, rews, means, targets=targets, chunk=chunk, want_logits=True)["logits"]
+    elif env.startswith("darkroom"):
         if context != "fresh":
             raise NotImplementedError("--context online is for the bandits: a DarkRoom rollout's context is the "
                                       "episode's own transitions, whose query state moves with it")
@@ -136,7 +168,9 @@ def main(argv=None):
     parser.add_argument("--sample", action="store_true", help="Unused (the online context is always sampled)")
     parser.add_argument("--save", type=str, default="figs/eval_posterior", help="Directory for the plot and the JSON")
     parser.add_argument("--env", type=str, default="bandit",
-                        choices=["bandit", "bandit_thompson", "darkroom", "darkroom_heldout"])
+                        choices=["bandit", "bandit_thompson", "linear_bandit", "darkroom", "darkroom_heldout"])
+    parser.add_argument("--data_type", choices=["thompson", "uniform"], default="thompson",
+                        help="linear_bandit, --context fresh: the generator's rollin")
     parser.add_argument("--context", type=str, default="fresh", choices=["fresh", "online"])
     parser.add_argument("--grid", type=int, default=None, help="Posterior grid size (default: posterior_grid)")
     parser.add_argument("--chunk", type=int, default=0, help="Tasks per launch (0: all at once)")
@@ -164,12 +198,14 @@ def main(argv=None):
     model.eval()
 
     res = run(model, env, args["context"], n_eval, dim, horizon, var, bandit_type, max(seed, 0), args["grid"],
-              args["chunk"])
+              args["chunk"], args["lin_d"], args["data_type"])
     summary = summarise(res)
     save = args["save"]
     plot_results(summary, os.path.join(save, "posterior_gap.png"))
     meta = {k: args[k] for k in ("env", "context", "n_eval", "H", "dim", "var", "seed", "grid")}
-    meta["bandit_type"] = None if darkroom else bandit_type
+    meta["bandit_type"] = None if darkroom or env == "linear_bandit" else bandit_type
+    if env == "linear_bandit":
+        meta.update(lin_d=args["lin_d"], data_type=args["data_type"])
     with open(os.path.join(save, "posterior_gap.json"), "w") as f:
         json.dump({"args": meta, **summary}, f)
     last = {k: summary[k]["mean"][-1] for k in KEYS}

@@ -21,13 +21,14 @@ data types; it collects 'thompson').  The two are different training distributio
 behaviour policy.  The arms are collect_data.py's (``RandomState(1234)``, ``--dim`` x ``--lin_d``), the file
 names and the extra checkpoint every 10 epochs are train.py's, and ``--shuffle`` is refused as train.py refuses it.
 
-``--bayes_floor`` (bandit, bandit_thompson, darkroom*): before epoch 1, the irreducible floor of the printed
-test loss, ``E[-log P(a* | D_t)]`` averaged over t = 1 .. H of the test samples (the same every epoch) under
+``--bayes_floor`` (bandit, bandit_thompson, darkroom*, linear_bandit at lin_d 2): before epoch 1, the
+irreducible floor of the printed test loss, ``E[-log P(a* | D_t)]`` averaged over t = 1 .. H of the test samples (the same every epoch) under
 the exact Bayes posterior of the optimal action (dpt_hip.fresh_posterior; the DarkRoom prior is the list the
 test samples are drawn from), printed and logged as one line ``\tBayes floor (test): ...``.  The test loss
-minus this floor is the mean KL from the posterior to the model.  Refused for linear_bandit: P(arm optimal)
-under its Gaussian posterior over theta is a lin_d-dimensional integral with no cheap form.  Without the flag
-the log and every file are as before.
+minus this floor is the mean KL from the posterior to the model.  linear_bandit has it at ``--lin_d 2`` with
+``--var`` > 0 (dpt_hip.linear_posterior: an angular quadrature, either ``--data_type``); otherwise it is refused:
+P(arm optimal) under the Gaussian posterior over theta is a lin_d-dimensional integral with no cheap form.
+Without the flag the log and every file are as before.
 """
 import argparse
 import hashlib
@@ -38,7 +39,8 @@ import numpy as np
 import torch
 
 import common_args
-from dpt_hip import FreshEnv, fresh_batch, fresh_posterior, posterior_compare, posterior_grid
+from dpt_hip import (FreshEnv, fresh_batch, fresh_posterior, linear_posterior_supported, posterior_compare,
+                     posterior_grid)
 from dpt_hip.train import FreshTrainer
 from models.net import Transformer
 from train_common import LossLog, set_seeds
@@ -88,7 +90,8 @@ def main(argv=None):
     parser.add_argument("--data_type", choices=["thompson", "uniform"], default=None,
                         help="linear_bandit only: the rollin, collect_data.py's data types")
     parser.add_argument("--bayes_floor", action="store_true",
-                        help="print the Bayes floor of the test loss before epoch 1 (bandit, bandit_thompson, darkroom*)")
+                        help="print the Bayes floor of the test loss before epoch 1 (bandit, bandit_thompson, darkroom*, "
+                             "linear_bandit at --lin_d 2 and --var > 0)")
     args = vars(parser.parse_args(argv))
     print("Args: ", args)
 
@@ -110,9 +113,10 @@ def main(argv=None):
         raise ValueError(f"--batch {batch}")
     if args["bayes_floor"]:
         if env == "linear_bandit":
-            raise NotImplementedError("--bayes_floor: the linear bandit's posterior over theta is Gaussian, but the "
-                                      "probability that an arm is optimal under it is a lin_d-dimensional integral "
-                                      "with no cheap form; the floor exists for bandit, bandit_thompson and darkroom*")
+            why = linear_posterior_supported(lin_d, var)
+            if why is not None:
+                raise NotImplementedError(f"--bayes_floor: {why}; the floor also exists for bandit, bandit_thompson "
+                                          "and darkroom*")
         if env in ("bandit", "bandit_thompson"):  # ValueError where the grid would under-resolve the posterior
             posterior_grid(var, horizon, "uniform" if env == "bandit" else "bernoulli")
 

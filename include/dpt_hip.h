@@ -67,7 +67,8 @@ extern "C" {
  * dpt_fresh_args, dpt_fresh_batch, dpt_fresh_step, dpt_fresh_eval_loss) and its linear-bandit twin
  * (dpt_fresh_linear_args, dpt_fresh_linear_batch, dpt_fresh_linear_step, dpt_fresh_linear_eval_loss); the
  * Bayes posterior of the optimal action (dpt_bandit_posterior_workspace_numel, dpt_bandit_posterior,
- * dpt_darkroom_posterior, dpt_posterior_compare) */
+ * dpt_darkroom_posterior, dpt_posterior_compare) and its linear-bandit twin at lin_d = 2
+ * (dpt_linear_posterior_workspace_numel, dpt_linear_posterior) */
 #define DPT_ABI_VERSION 8
 
 /* error codes (mapped to the reference's Python exceptions by dpt_hip/_lib.py) */
@@ -1116,6 +1117,74 @@ typedef struct dpt_posterior_compare_args {
 /* One launch, one thread per row.  DPT_EINVAL: null args / post / logits / targets, N < 1, T < 1, A < 1,
  * non-zero flags.  DPT_EUNSUPPORTED: A > 32. */
 int dpt_posterior_compare(const dpt_posterior_compare_args* args_host, void* stream);
+
+/* ------------------------------------------------------------------ Linear bandit, lin_d = 2
+ * The posterior of the optimal arm of the linear bandit (reward = x_a . theta + var * normal) for arms in the
+ * plane, on every prefix of a record.  The posterior of theta is a 2-D Gaussian N(m, S), the regions where an
+ * arm is optimal are wedges through theta = 0, and along a ray from m the winner is the upper envelope of A
+ * straight lines: a 1-D angular quadrature of positive terms.  ABI 8, additive.
+ * tests/linear_posterior_oracle.py restates the definition in numpy.
+ *   inputs   arms X (A, 2) fp64, actions (N, H) int32, rewards (N, H) fp64, var > 0 (the noise std), G
+ *   prior    theta ~ N(0, I / 2) (sample_linear's normal / sqrt(lin_d)): precision 2 I
+ *   grid     G a multiple of 64 in [64, 65536]; phi_i = (6.283185307179586 * (i + 0.5)) / G,
+ *            omega_i = (cos phi_i, sin phi_i)
+ * All arithmetic in fp64, no fused multiply-add, every expression in the order written here.
+ *   statistics of row t, over the pulls j < t IN PULL ORDER with x = X[actions[j]], r = rewards[j],
+ *            v2 = var * var (an action outside [0, A) adds nothing):
+ *              sxx += (x0 * x0) / v2   sxy += (x0 * x1) / v2   syy += (x1 * x1) / v2
+ *              b0  += (r * x0) / v2    b1  += (r * x1) / v2
+ *   moments    l00 = 2 + sxx   l01 = sxy   l11 = 2 + syy   det = l00 * l11 - l01 * l01
+ *              S00 = l11 / det   S01 = -(l01 / det)   S11 = l00 / det
+ *              m0 = S00 * b0 + S01 * b1   m1 = S01 * b0 + S11 * b1
+ *              L00 = sqrt(S00)   L10 = S01 / L00   L11 = 1 / sqrt(l11)        (S = L L^T, L lower)
+ *   per arm    alpha_a = x0 * m0 + x1 * m1   xl0_a = x0 * L00 + x1 * L10   xl1_a = x1 * L11
+ *              beta_a(i) = xl0_a * cos phi_i + xl1_a * sin phi_i
+ *   ray i      arm a holds the radii [lo, hi] of theta = m + r L omega_i:
+ *              lo = max(0, max over b with beta_a > beta_b of (alpha_b - alpha_a) / (beta_a - beta_b))
+ *              hi = min over b with beta_a < beta_b of (alpha_a - alpha_b) / (beta_b - beta_a), +inf if none
+ *              empty if hi <= lo, or if some b has beta_b == beta_a and either alpha_b > alpha_a or
+ *              alpha_b == alpha_a with b < a (ties to the lower index, as np.argmax)
+ *              mass_a(i) = exp(-(lo * lo) / 2) - exp(-(hi * hi) / 2)
+ *   output     u_a = sum_i mass_a(i), post[n][t][a] = u_a / sum_b u_b, (N, H + 1, A) fp64
+ * Rows before the first valid pull (m = 0 exactly: the rule would only count grid directions, an O(1 / G)
+ * error) are the prior in closed form, computed once per call from the arms alone:
+ *   prior_a = angle of {psi : a = argmax_b x_b . (cos psi, sin psi), ties to the lower index} / 6.283185307179586
+ *            the set is the intersection over b != a of the open half-circles centred at theta_b =
+ *            atan2(x_a1 - x_b1, x_a0 - x_b0) (an identical arm b: empty if b < a, else no constraint); with
+ *            delta_b = theta_b - theta_first wrapped into (-pi, pi] its angle is
+ *            (pi - max(0, max_b delta_b)) + min(0, min_b delta_b); below 2^-40 it counts as 0; A == 1: 1
+ * An arm whose prior is 0 is optimal on a null set only (strictly inside the hull of the arms, a copy of a
+ * lower arm, or inside an edge of the hull, where the sign of hi - lo would be rounding noise on every ray): it
+ * is dropped -- every row of it is exactly 0 and it bounds no other arm on any ray.  Its pulls still count in
+ * the statistics.
+ * The reduction order is fixed (a thread's rays in index order, a butterfly per wave, the waves in order, the
+ * kept arms in index order): repeated calls are bit-identical and a task's rows do not depend on N or on how
+ * the caller chunks the tasks.
+ * Known limit: a row whose posterior mean lies within about 1 / G posterior standard deviations of theta = 0
+ * has the prior rows' sharp transitions; for t >= 1 that is an event of probability about 1 / G^2.        */
+typedef struct dpt_linear_posterior_args {
+    int32_t N;                 /* tasks                                                             */
+    int32_t H;                 /* recorded pulls per task (>= 0): rows 0 .. H                       */
+    int32_t A;                 /* arms, <= 32                                                       */
+    int32_t lin_d;             /* 2                                                                 */
+    int32_t G;                 /* rays: a multiple of 64 in [64, 65536]                             */
+    int32_t flags;             /* 0                                                                 */
+    double var;                /* reward std, > 0                                                   */
+    const double* arms;        /* (A, 2)                                                            */
+    const int32_t* actions;    /* (N, H) (NULL when H = 0)                                          */
+    const double* rewards;     /* (N, H)                                                            */
+    double* workspace;         /* dpt_linear_posterior_workspace_numel doubles                      */
+    double* post;              /* (N, H + 1, A)                                                     */
+} dpt_linear_posterior_args;
+
+/* doubles of workspace: the rays' cos | sin tables (2 G), then the prior (32), the kept arms' count (1, then
+ * 7 of padding), their indices (32) and the rank of every arm among them (32); the same for every N */
+int dpt_linear_posterior_workspace_numel(int32_t N, int32_t A, int32_t lin_d, int32_t G, int64_t* numel_out_host);
+/* Two launches (the tables and the prior, then the rows), no host synchronisation, no allocation.  Host
+ * checks fail before any launch.  DPT_EINVAL: null args / arms / workspace / post, null actions or rewards
+ * while H > 0, N < 1, H < 0, A < 1, lin_d < 1, G < 1, var <= 0, non-zero flags, a workspace that is not
+ * 8-byte aligned.  DPT_EUNSUPPORTED: lin_d != 2, A > 32, a G that is not a multiple of 64 in [64, 65536]. */
+int dpt_linear_posterior(const dpt_linear_posterior_args* args_host, void* stream);
 
 /* ------------------------------------------------------------------ image-conditioned DPT (ImageTransformer)
  * models/net.py:63-132: per token an image (3, 25, 25) goes through Conv2d(3,16,k3,s2) -> ReLU ->
